@@ -18,7 +18,14 @@ pairing waves share the SIMDs with the next one's and each batch's fold,
 comparison and launch gaps hide behind the others' pairing kernels
 (--inflight 1: one batch at a time, the `sequential` sub-line).
 
-Sub-lines (never `value`):
+A plain run sets up, warms up, times --steps headline steps, checks their
+verdicts and prints the headline's line; --dump-outputs DIR also writes the
+last timed step's verdict codes and packed bitset as DIR/<name>.npy (float32;
+the inputs are seeded, so two builds can be compared output for output).
+--full adds everything below: the per-kernel phases and rooflines, the CPU
+baselines and the sub-lines.
+
+Sub-lines (--full; never `value`):
   sequential      the headline batch one at a time on the context's stream
   single          config 2: 4096 independent single-signature checks
                   (simul/p2p/aggregator.go:244 verifyPacket)
@@ -549,6 +556,26 @@ def _dev_bytes(b: bytes, dev):
     return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: every array as path/<name>.npy in float32 (verdict codes
+    and bitset bytes are small integers: exact), DUMP_MAX_BYTES in all; an
+    array over its share is cut to a fixed, seeded sample of its elements
+    (sorted indices, the same on every run). Returns {name: elements written}."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 4 // max(1, len(arrays))
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(20).choice(a.size, size=cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+        out[name] = int(a.size)
+    return out
+
+
 class AggregateWorkload:
     """Config 3 (or 5): n multisignatures on an n_reg-key registry per rank."""
 
@@ -961,19 +988,27 @@ def main():
                          "oracle-made workload exactly as the bench does after its timed regions, print rank 0's line")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the sequential line, per-kernel phases and rooflines, the sub-lines "
+                         "and the CPU baselines (--no-cpu, --no-extra, --no-service, --pipeline, --pipeline-overlap and "
+                         "--cpu-sample shape these and do nothing without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step (codes and packed bitset) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--committees", action="store_true",
                     help="config 5: each rank is one committee of 4096 signers (own 4096-key registry)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline only (no single / full / pipelined lines)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no sub-lines (single / full_registry / pipelined / ...); the headline's own "
+                         "rooflines stay")
     ap.add_argument("--inflight", type=int, default=None,
                     help="headline: batches in flight on the context's lanes (1: one batch at a time on the "
                          "context's stream; default 4; 1 in the gloo rehearsal)")
-    ap.add_argument("--pipeline", type=int, default=2, help="batches in flight for the 'pipelined' line (1: skip)")
+    ap.add_argument("--pipeline", type=int, default=2, help="with --full: batches in flight for the 'pipelined' line (1: skip)")
     ap.add_argument("--pipeline-overlap", type=int, default=1,
-                    help="the pipelined line's contexts run their fold beside the pairing kernel (1) or before it (0)")
-    ap.add_argument("--cpu-sample", type=int, default=4096, help="requests in the CPU baseline's sample")
-    ap.add_argument("--no-service", action="store_true", help="skip the config-4 process-model lines")
+                    help="with --full: the pipelined line's contexts run their fold beside the pairing kernel (1) or "
+                         "before it (0)")
+    ap.add_argument("--cpu-sample", type=int, default=4096, help="with --full: requests in the CPU baseline's sample")
+    ap.add_argument("--no-service", action="store_true", help="with --full: skip the config-4 process-model lines")
     ap.add_argument("--prewarm", type=float, default=0.3,
                     help="seconds of untimed headline steps before the warmup steps (GPU clocks settle)")
     args = ap.parse_args()
@@ -1124,6 +1159,56 @@ def main():
             assert torch.equal(g.cpu(), want), f"gathered bitset of rank {r} differs"
     for ln in lanes:
         ln.close()
+    value = n * args.steps * world / dt
+    workload = (f"config 5: one committee of {n_reg} signers per GPU, {n} multisigs at random Handel levels"
+                if args.committees else
+                f"config 3: {n} Handel multisigs per GPU on a {n_reg}-key registry, random node/level")
+    # the headline's own figures: all a plain run prints
+    line = {
+        "metric": "BN254 aggregate-sig verifications/sec (batch 4096)",
+        "value": round(value, 1),
+        "unit": "verifications/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "batches_in_flight": inflight,
+        "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+        "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
+        "timed_region_ns": head_marks,
+        "prewarm": {"seconds": args.prewarm, "steps": prewarm_steps, "what": "untimed headline steps before the "
+                    "warmup steps (GPU clocks settled whatever the warmup count)"},
+        "gather": {**gather_check, "what": "every rank's all-gathered verdict bitset checked against the expected "
+                   "one (world 1: the gather is the identity, the rank's own bitset is checked)"},
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32 (26-bit-limb Fp, 64-bit accumulators)",
+        "data": "synthetic (seeded keys, lib.Message, bitset density U[0.5,1], 1/8 tampered aggregates)",
+        "config": {"workload": workload + ", bitset density U[0.5,1], 1/8 tampered",
+                   "batch_per_gpu": n, "registry": n_reg, "message": "lib.Message (81 B)",
+                   "signers_per_check_mean": round(float(head.signers.mean()), 1),
+                   "signers_per_check_max": int(head.signers.max()),
+                   "parallelism": f"dp{world} (batches per GPU, {inflight} in flight on the context's lanes; RCCL "
+                                  "all_gather of verdict bitsets)"},
+        "setup": {"ms": round(head.setup_ms, 2), "what": "per (message, registry), outside the timed "
+                  f"region: e(H, pk_i) for {n_reg} keys + GT products of every 16-key window subset and aligned "
+                  "block (hg_prepare_aggregate)",
+                  "cold_value": round(n / ((head.setup_ms + dt / args.steps * 1e3) * 1e-3), 1)},
+        "full": args.full,
+    }
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step handed its caller: that lane's verdict codes
+        # and their packed bitset (rank 0's; every rank's inputs are seeded)
+        last = lane_out[(turn[0] - 1) % inflight] if lanes else (None, head.d_codes, head.d_bits, gathered)
+        line["outputs"] = dump_outputs(args.dump_outputs, {"verdict_codes": last[1], "verdict_bitset": last[2]})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        eng.close()
+        if dist:
+            tdist.destroy_process_group()
+        return
     sequential = None
     progress("headline done; sequential, per-kernel phases")
     if inflight > 1 and not args.no_extra:
@@ -1139,7 +1224,6 @@ def main():
     eng.set_fold_overlap(False)
     ph_seq = timed_phases(eng, lambda: [head.submit() for _ in range(5)])
     eng.set_fold_overlap(True)
-    value = n * args.steps * world / dt
     # the dominant kernels of the step: the GT fold (plan, chunks, combine) and
     # the pairing check, on the work they implement (the primary roofline).
     # Time base: with batches in flight the kernels of different batches
@@ -1403,50 +1487,17 @@ def main():
     cpu = cpu_baseline_on_rank0(rank, dist, args, lambda: cpu_baseline_aggregate(
         head.reg, head.reqs, head.words, head.sigs, head.expect, args.cpu_sample))
     if rank == 0:
-        workload = (f"config 5: one committee of {n_reg} signers per GPU, {n} multisigs at random Handel levels"
-                    if args.committees else
-                    f"config 3: {n} Handel multisigs per GPU on a {n_reg}-key registry, random node/level")
-        line = {
-            "metric": "BN254 aggregate-sig verifications/sec (batch 4096)",
-            "value": round(value, 1),
-            "unit": "verifications/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "batches_in_flight": inflight,
-            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-            "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
-            "timed_region_ns": head_marks,
-            "prewarm": {"seconds": args.prewarm, "steps": prewarm_steps, "what": "untimed headline steps before the "
-                        "warmup steps (GPU clocks settled whatever the warmup count)"},
-            "gather": {**gather_check, "what": "every rank's all-gathered verdict bitset checked against the expected "
-                       "one (world 1: the gather is the identity, the rank's own bitset is checked)"},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32 (26-bit-limb Fp, 64-bit accumulators)",
-            "data": "synthetic (seeded keys, lib.Message, bitset density U[0.5,1], 1/8 tampered aggregates)",
-            "config": {"workload": workload + ", bitset density U[0.5,1], 1/8 tampered",
-                       "batch_per_gpu": n, "registry": n_reg, "message": "lib.Message (81 B)",
-                       "signers_per_check_mean": round(float(head.signers.mean()), 1),
-                       "signers_per_check_max": int(head.signers.max()),
-                       "parallelism": f"dp{world} (batches per GPU, {inflight} in flight on the context's lanes; RCCL "
-                                      "all_gather of verdict bitsets)"},
+        line.update({
             "roofline": roof,
             "effective_rate": effective,
             "roofline_k_verify": roof_verify,
             "roofline_k_verify_sig12": roof_sig12,
             "roofline_gt_fold": roof_fold,
-            "setup": {"ms": round(head.setup_ms, 2), "what": "per (message, registry), outside the timed "
-                      f"region: e(H, pk_i) for {n_reg} keys + GT products of every 16-key window subset and aligned "
-                      "block (hg_prepare_aggregate)",
-                      "cold_value": round(n / ((head.setup_ms + dt / args.steps * 1e3) * 1e-3), 1)},
             "cpu_baseline": cpu,
             "gpu_over_cpu": (round(value / cpu["value"], 1) if cpu and cpu.get("value") else None),
             "sequential": sequential,
             **extra,
-        }
+        })
         print(json.dumps(line))
     eng.close()
     if dist:

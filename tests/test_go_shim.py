@@ -4,19 +4,24 @@ There is no Go toolchain here, so the Go files are never compiled. What can be
 checked without one: every C identifier the cgo code uses is declared in
 include/handel_gpu.h (and exported by the built library), the error texts the
 Go tests expect are the ones hg_code_string returns, and the Handel config
-hook patch applies to the reference's config.go / handel.go.
+hook patch applies to the reference's config.go / handel.go (pinned by
+recorded digests of the lines it touches, tests/golden/).
 """
 
 import ctypes
+import json
 import os
 import re
-import shutil
-import subprocess
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GO = os.path.join(ROOT, "go")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import reference_digests as RD  # noqa: E402  (the golden file's recorder: its digest and patch reader)
+
 HEADER = (open(os.path.join(ROOT, "include", "handel_gpu.h")).read() +
           open(os.path.join(ROOT, "include", "handel_client.h")).read())
 
@@ -99,25 +104,29 @@ def test_go_expected_error_texts_match_abi():
     assert "handel: bn256: signature invalid" in abi
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference") or shutil.which("patch") is None,
-                    reason="reference tree or patch(1) absent")
-def test_config_hook_patch_applies(tmp_path):
-    for f in ("config.go", "handel.go"):
-        shutil.copy(os.path.join("/root/reference", f), tmp_path / f)
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(GO, "handel", "config_hook.patch")],
-                       cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+def test_config_hook_patch_applies():
+    """Every hunk of the config hook finds, at the line its header names, the
+    lines the reference's config.go / handel.go hold there: their digests are
+    recorded in tests/golden/reference_go_digests.json
+    (tools/reference_digests.py made it from a reference tree), so
+    the patch applies there without offset or fuzz."""
+    want = json.load(open(RD.OUT))["patch_preimage"]
+    hunks = RD.patch_hunks()
+    assert sorted({f for f, _, _ in hunks}) == ["config.go", "handel.go"]
+    assert len(hunks) == len(want)
+    for f, start, pre in hunks:
+        assert want[f"{f}:{start}:{len(pre)}"] == RD.digest("\n".join(pre)), (f, start)
 
 
 def test_batched_processing_uses_reference_internals():
     """batched_processing.go relies only on package-handel names that exist in
-    the reference (read as text when the tree is present)."""
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference tree absent")
+    the reference: of the identifiers the file uses, the ones the reference's
+    package-handel sources hold too are recorded, as digests, in
+    tests/golden/reference_go_digests.json."""
     src = open(os.path.join(GO, "handel", "batched_processing.go")).read()
-    ref = "".join(open(os.path.join("/root/reference", f)).read()
-                  for f in os.listdir("/root/reference") if f.endswith(".go"))
+    known = set(json.load(open(RD.OUT))["identifiers"])
     for name in ("incomingSig", "deathPillPair", "newIndividualSigFilter", "signatureProcessing", "SigEvaluator",
                  "Partitioner", "IdentitiesAt", "Logger", "Filter", "MultiSignature", "Identity"):
         assert name in src
-        assert re.search(r"\b%s\b" % name, ref), name
+        assert RD.digest(name)[:12] in known, name
+    assert RD.digest("newBatchedProcessing")[:12] not in known  # the recorded set tells names apart

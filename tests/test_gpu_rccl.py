@@ -36,7 +36,7 @@ def test_rccl_branch_world_one():
     env.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                HG_BENCH_FORCE_PG="1")
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1",
-                        "--prewarm", "0.05", "--no-extra", "--no-cpu"],
+                        "--prewarm", "0.05"],  # a plain run: the headline alone
                        capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Headline A/B of library variants (handel_amd/_build/variants/*.so, built
-# from earlier commits) against the in-tree library, interleaved.
+# from earlier commits) against the in-tree library, interleaved
+# (bench.py --full: the summary reads the per-kernel figures; AB_FLAGS
+# replaces --no-cpu --no-extra, --full stays).
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 R=${1:-r03s}
@@ -11,7 +13,7 @@ for rep in 1 2 3; do
   for v in ${VARIANTS:-lazy lazyef cur}; do
     lib=$V/libhandel_gpu_$v.so
     [ $v = cur ] && lib=handel_amd/_build/libhandel_gpu.so
-    HG_LIB=$lib timeout -k 10 240 python -u bench.py --steps ${AB_STEPS:-100} --warmup 20 ${AB_FLAGS:---no-cpu --no-extra} > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
+    HG_LIB=$lib timeout -k 10 240 python -u bench.py --full --steps ${AB_STEPS:-100} --warmup 20 ${AB_FLAGS:---no-cpu --no-extra} > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
     echo "$v $rep done"
   done
 done

@@ -1,7 +1,9 @@
 #!/bin/bash
 # Headline A/B of one environment switch, interleaved on one box:
 #   AB_VAR=HG_SIG12_SPLIT AB_VALUES="1 0" tools/gpu_ab_env.sh TAG
-# (bench.py --no-cpu --no-extra, 100 timed steps, three rounds), then the
+# (bench.py --full --no-cpu --no-extra: the headline with its rooflines and
+# per-kernel figures; 100 timed steps, three rounds; AB_FLAGS replaces the
+# two trimming options, --full stays), then the
 # pairing kernels alone (tools/probe_sig12.py) per value.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
@@ -11,7 +13,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 for rep in 1 2 3; do
   for v in ${AB_VALUES:-1 0}; do
-    env $AB_VAR=$v timeout -k 10 240 python -u bench.py --steps ${AB_STEPS:-100} --warmup 20 ${AB_FLAGS:---no-cpu --no-extra} > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
+    env $AB_VAR=$v timeout -k 10 240 python -u bench.py --full --steps ${AB_STEPS:-100} --warmup 20 ${AB_FLAGS:---no-cpu --no-extra} > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
   done
 done
 for v in ${AB_VALUES:-1 0}; do

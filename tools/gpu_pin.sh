@@ -1,6 +1,7 @@
 #!/bin/bash
 # The bench line pinned to a profile of the same invocation:
-#  1. the driver's invocation, plain (bench.json);
+#  1. the --full line (headline, rooflines, sub-lines, CPU baseline) at the
+#     driver's step counts, unprofiled (bench.json);
 #  2. the same invocation under --kernel-trace --stats: its bench line and its
 #     per-kernel averages come from ONE run (bench_traced.json, *_driver_ktrace_stats.csv);
 #     and the per-step device-busy time of its timed region (tools/busy_summary.py:
@@ -15,9 +16,9 @@ R=${1:-r05}
 OUT=gpurun_out/pin_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-D="bench.py --steps 20 --warmup 5"
-H="bench.py --steps 20 --warmup 5 --no-cpu --no-extra"
-S="bench.py --steps 5 --warmup 1 --no-cpu --no-service --pipeline 1"
+D="bench.py --full --steps 20 --warmup 5"
+H="bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra"
+S="bench.py --full --steps 5 --warmup 1 --no-cpu --no-service --pipeline 1"
 K="k_verify_sig|k_sig_|k_sig12|k_gt_|k_agg_"
 timeout -k 10 600 python3 $D > $OUT/bench.json 2> $OUT/bench.err &&
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OUT/ktrace -o run -- python3 $D > $OUT/bench_traced.json 2> $OUT/traced.err &&

@@ -7,7 +7,7 @@ R=${1:-r06d}
 OUT=gpurun_out/pmc_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-H="bench.py --steps 20 --warmup 5 --no-cpu --no-extra"
+H="bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra"
 K="k_verify_sig|k_sig_|k_sig12|k_gt_|k_agg_"
 timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$K" -d $OUT/fetch -o run -- python3 $H > $OUT/fetch.log 2>&1 &&
 timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$K" -d $OUT/write -o run -- python3 $H > $OUT/write.log 2>&1 &&

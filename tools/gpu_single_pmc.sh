@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=${1:-r05s}
 OUT=gpurun_out/single_$R
 mkdir -p $OUT
-S="bench.py --steps 5 --warmup 1 --no-cpu --no-service --pipeline 1"
+S="bench.py --full --steps 5 --warmup 1 --no-cpu --no-service --pipeline 1"
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_verify<" -d $OUT/fetch -o run -- python3 $S > $OUT/fetch.log 2>&1 &&
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_verify<" -d $OUT/write -o run -- python3 $S > $OUT/write.log 2>&1 &&
 mkdir -p $OUT/ktrace && cp -r $OUT/fetch/* $OUT/ktrace/ 2>/dev/null; python3 - $OUT $OUT/${R} <<'PY'
