@@ -179,10 +179,13 @@ HG_DEV void acc_mad_pinned(Acc& a, const Fp& x, const Fp& y) {
     }
 }
 // REDC digits interleaved with the job's last product (acc_mad_redc) where the
-// generator sets a round's FU flag (the pairing kernels' single-job rounds:
-// one wave per SIMD has nothing else to hide the reduction's serial chain
-// behind; the GT fold runs several waves per SIMD and keeps the
-// products-then-REDC order). HG_REDC_FUSE=0 builds that order everywhere.
+// generator sets a round's FU flag (its REDC_FUSE table, per program): the
+// single-job rounds of the kernels that run one wave per SIMD (k_verify_sig's
+// 16-lane programs), which have nothing else to hide the reduction's serial
+// chain behind. The GT fold runs several waves per SIMD and the 12-lane
+// pairing kernels two, from different batches: their programs keep the
+// products-then-REDC order (every product a Karatsuba product, where KS is
+// set). HG_REDC_FUSE=0 builds that order everywhere.
 #ifndef HG_REDC_FUSE
 #define HG_REDC_FUSE 1
 #endif
@@ -213,7 +216,8 @@ HG_DEV void x_products(const Team& T, const uint32_t (&w)[W], int base, Acc& acc
   }
 }
 // Karatsuba products (the generator's per-job flag KS: jobs of 4+ products,
-// where the combination's ~55 instructions are repaid): with x = x0 +
+// where the combination's ~55 instructions are repaid; 3+ in the 12-lane
+// cyclotomic squaring, KARATSUBA_MIN_PROG): with x = x0 +
 // 2^130 x1, y = y0 + 2^130 y1 (5-limb halves), a product is x0 y0, x1 y1 and
 // (x0 + x1)(y0 + y1) - x0 y0 - x1 y1: 75 mads instead of 100, plus 10 limb
 // additions. The three half-products accumulate over the whole job in their

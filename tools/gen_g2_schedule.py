@@ -392,8 +392,16 @@ def prog_cyc_sqr_x_shared():
         3(a^2 + xi b^2).y  b-part:  9 by^2 -  6 bx by - 9 bx^2 = by V1 + (-bx) V2
     with V1 = 9 by - 3 bx, V2 = 9 bx + 3 by, uses three values (V1, V2, -bx)
     where CYC_SQR_X uses five (18 bx, 3(by + bx), by - bx, -6 bx,
-    9(by + bx)); the xi lanes of group 2 share -bx. Still at most three
-    products per lane, plus -2c / +2c as a linear term."""
+    9(by + bx)). The product lanes take their sign from -bx as well,
+        6ab.y = (6ay) by + (6ax)(-bx),
+    and the xi lanes keep the factor 6 on the plain element,
+        6 xi ab.x = (6ax) W1 + (6ay) W2       W1 = 3 by - bx
+        6 xi ab.y = (6ay) W1 + (6ax)(-W2)     W2 = by + 3 bx,
+    so no value carries a coefficient above 9 or a negation above 4: with the
+    round's correction 4 (4p)'' every limb stays below 2^31, the 5-limb half
+    sums below 2^32, and the round's 3-product jobs run as Karatsuba products
+    (KARATSUBA_MIN_PROG). Still 24 values and at most three products per
+    lane, plus -2c / +2c as a linear term."""
     def e(name, c):
         return comp(name, c)
 
@@ -418,15 +426,15 @@ def prog_cyc_sqr_x_shared():
                 if c == "x":
                     slots = [([(ax, 6)], [(by, 1)]), ([(ay, 6)], [(bx, 1)])]
                 else:
-                    slots = [([(ay, 6)], [(by, 1)]), ([(ax, -6)], [(bx, 1)])]
+                    slots = [([(ay, 6)], [(by, 1)]), ([(ax, 6)], nbx)]
                 lin = [(e(f"A{k}", c), 2)]
             else:
-                u = [(ax, 18), (ay, 6)]
-                v = [(ay, 18), (ax, -6)]
+                w1 = [(by, 3), (bx, -1)]
+                w2 = [(by, 1), (bx, 3)]
                 if c == "x":
-                    slots = [(u, [(by, 1)]), (v, [(bx, 1)])]
+                    slots = [([(ax, 6)], w1), ([(ay, 6)], w2)]
                 else:
-                    slots = [(v, [(by, 1)]), (u, nbx)]
+                    slots = [([(ay, 6)], w1), ([(ax, 6)], neg(w2))]
                 lin = [(e(f"A{k}", c), 2)]
             lanes.append(Lane(comp(f"D{k}", c), slots + [(lin, one())]))
     return [lanes]
@@ -787,9 +795,10 @@ class XRound:
         return b
 
 
-def compile_round(lanes, name, scratch_cap, lanes2=None, pre_lanes=16):
+def compile_round(lanes, name, scratch_cap, lanes2=None, pre_lanes=16, ks_min=None):
     """pre_lanes: lanes that evaluate the pre-pass values (16, or 12 for
-    programs that also run in 12-lane teams: PRE_LANES)."""
+    programs that also run in 12-lane teams: PRE_LANES); ks_min: the program's
+    Karatsuba threshold (KARATSUBA_MIN_PROG, default KARATSUBA_MIN)."""
     one_lc = [(REG["ONE"], 1)]
     values = {}      # canonical lincomb -> scratch code
     order = []
@@ -871,16 +880,19 @@ def compile_round(lanes, name, scratch_cap, lanes2=None, pre_lanes=16):
     xr = XRound(nv, nt, np_, nl, out, name, np2, nl2)
     xr.ef = ef
     try:
-        check_xround(xr, order)
+        check_xround(xr, order, ks_min)
     except AssertionError:
         # the round-uniform correction overflows a bound: per-lane corrections
         xr.kp = xr.kl1 = xr.kl2 = -1
-        check_xround(xr, order)
+        check_xround(xr, order, ks_min)
     return xr
 
 
-def check_xround(xr, order):
-    """Limb sums < 2^32, 64-bit columns < 2^64, REDC input < 800 p^2."""
+def check_xround(xr, order, ks_min=None):
+    """Limb sums < 2^32, 64-bit columns < 2^64, REDC input < 800 p^2.
+    ks_min: the program's Karatsuba threshold (default KARATSUBA_MIN)."""
+    if ks_min is None:
+        ks_min = KARATSUBA_MIN
     def src_bound(code):
         if code >= X_SCR:
             return vbound[code]
@@ -903,10 +915,10 @@ def check_xround(xr, order):
     jobs = [(L["prod"], L["lin"], xr.kl1, xr.nl) for L in xr.lanes]
     if xr.fused:
         jobs += [(L["prod2"], L["lin2"], xr.kl2, xr.nl2) for L in xr.lanes]
-    # Karatsuba per job (bn256_xprog.h x_products_ks): worth it from
-    # KARATSUBA_MIN products, valid while the 5-limb half sums stay 32-bit
+    # Karatsuba per job (bn256_xprog.h x_products_ks): worth it from the
+    # program's threshold on, valid while the 5-limb half sums stay 32-bit
     def ks_ok(prods):
-        return len(prods) >= KARATSUBA_MIN and all(
+        return len(prods) >= ks_min and all(
             max(lb[i] + lb[i + 5] for i in range(5)) < 1 << 32
             for u, v in prods for lb in (src_bound(u)[1], src_bound(v)[1]))
     xr.ks1 = int(all(ks_ok(L["prod"]) for L in xr.lanes))
@@ -978,6 +990,16 @@ X_FETCH_WORDS = 16  # words per lane one table prefetch brings in (>= the widest
 # run in 12-lane teams (five per wave: k_gt_chunks, make_team12)
 PRE_LANES = {"MUL12F": 12, "SQR12_12": 12, "LINE_FIX_12": 12, "MUL12_12": 12, "CYC_SQR_X_12": 12}
 KARATSUBA_MIN = 4   # jobs of this many products use Karatsuba (when check_xround allows)
+# Per-program thresholds. The default counts instructions: a Karatsuba product
+# saves 25 mads for 10 limb additions, and the job's column combination (~55
+# plain instructions) is repaid from four products on. The 12-lane cyclotomic
+# squaring's 3-product jobs do not save instructions that way (SQ_INSTS_VALU
+# of k_sig12_fe: 160.5 M -> 159.4 M per 4096 checks, with lever A), but the
+# kernel is shorter with them beside a second wave on the SIMD: the threshold
+# 3 rests on the interleaved A/B alone (profiles/r07ks_levers_ab.json,
+# r07ks_ab.json), not on a cycle price of the two instruction classes, which
+# nobody has measured in these kernels.
+KARATSUBA_MIN_PROG = {"CYC_SQR_X_12": 3}
 # FE: the register file from register 2 on; ML: slots C..J during the Miller loop
 # FOLD: the GT fold kernels' compact team region (bn256_gt.hip): slots F, A, B,
 # then registers ZERO and ONE, then the pre-pass scratch
@@ -1025,7 +1047,8 @@ def compile_all():
         if name in FUSED:
             X[name] = _compile_fused(name, ctx)
         else:
-            X[name] = [compile_round(r, f"{name}[{i}]", SCRATCH_CAP[ctx], pre_lanes=PRE_LANES.get(name, 16))
+            X[name] = [compile_round(r, f"{name}[{i}]", SCRATCH_CAP[ctx], pre_lanes=PRE_LANES.get(name, 16),
+                                     ks_min=KARATSUBA_MIN_PROG.get(name))
                        for i, r in enumerate(PROGRAMS[name])]
     return X
 
@@ -1409,6 +1432,23 @@ SIG_PROGRAMS = ("SDBL", "LFEV", "FEVAL", "LINE_FIX", "MUL12", "CYC_SQR_X", "CYC_
                 "SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12")
 
 
+# REDC fusion (x_round's FU, bn256_xprog.h x_job): the job's last product runs
+# as a 100-mad schoolbook product with the REDC digits interleaved, which hides
+# the reduction's serial chain where a SIMD has one wave: k_verify_sig's
+# 16-lane rounds (layout S) and the final exponentiation's. Not the GT fold's
+# (several waves per SIMD hide the chain), not two-job rounds, not the pk-side
+# G2 steps (measured: config 2 0.5 % slower with them,
+# profiles/r03fuse_redc_ab.json). The 12-lane programs of k_sig12_miller and
+# k_sig12_fe always share their SIMD with a second wave, which hides the chain
+# as well, so the programs of REDC_FUSE_OFF keep the products-then-REDC order
+# and every product of theirs is a 75-mad Karatsuba product (measured, with
+# the cyclotomic squaring's third product fused and not:
+# profiles/r07ks_levers_ab.json).
+REDC_FUSE_OFF = ("SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12")
+REDC_FUSE = {name: (ctx == "FE" or name in SIG_PROGRAMS) and name not in REDC_FUSE_OFF
+             for name, ctx in X_PROGRAMS.items()}
+
+
 def touched(bx):
     """Largest team element index a bound round reads or writes."""
     m = 0
@@ -1476,12 +1516,7 @@ def emit_x(X, path):
             nxt = f"XHint{{{rounds[i + 1][1]}, {rounds[i + 1][0].words()}}}" if i + 1 < len(rounds) else "h"
             lz = int(name in LAZY_PROGRAMS and bx.nl > 0)
             assert not (lz and bx.fused), "a lazy round is not fused"
-            # FU: REDC interleaved with the last product (bn256_xprog.h x_job):
-            # the final exponentiation's and the sig-only Miller loop's rounds;
-            # not the GT fold's (several waves per SIMD hide the chain), not
-            # two-job rounds, not the pk-side G2 steps (measured: config 2
-            # 0.5 % slower with them, profiles/r03fuse_redc_ab.json)
-            fu = int(not bx.fused and (ctx == "FE" or name in SIG_PROGRAMS))
+            fu = int(REDC_FUSE[name] and not bx.fused)  # a two-job round never fuses
             calls.append(f"x_round<{bx.nv}, {bx.nt}, {bx.np}, {bx.nl}, {bx.words()}, {bx.np2}, {bx.nl2}, "
                          f"{bx.kp}, {bx.kl1}, {bx.kl2}, {bx.ks1}, {bx.ks2}, {lz}, {bx.ef}, {fu}>(T, S, {off}, {nxt});")
         args = ", ".join(f"S_{b}" for b in binding)
