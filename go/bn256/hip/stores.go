@@ -1,0 +1,162 @@
+package hip
+
+/*
+#include <stdlib.h>
+#include "handel_gpu.h"
+*/
+import "C"
+
+import (
+	"unsafe"
+)
+
+// Stores is the device-resident scoring state of the Handel instances one
+// process hosts (hg_stores_*): per receiver and level the best bitset, whether
+// there is one, and the verified individual signatures (store.go:39-80). The
+// host store stays authoritative: Store / unsafeCheckMerge (store.go:82-226)
+// run on the host once per verified signature and the changed levels are
+// pushed with Update; only Evaluate (store.go:101-183), which runs once per
+// queued signature per step, runs on the device.
+//
+// A Stores belongs to the registry its engine held when it was made: after a
+// later LoadRegistry every call fails. Close it before its engine.
+type Stores struct {
+	e      *Engine
+	h      *C.hg_stores
+	stride int
+}
+
+// StoreUpdate is the new state of one (receiver, level): Best nil means the
+// level has no best multisignature. Both bitsets are willf words of the
+// level's size (bit i = word[i>>6] bit i&63).
+type StoreUpdate struct {
+	Receiver, Level int
+	Best            []uint64
+	Individuals     []uint64
+}
+
+// NewStores creates the stores of the hosted receivers (distinct registry
+// indices); maxPackets sizes the workspaces of Evaluate and SelectDevice.
+func (e *Engine) NewStores(receivers []int, maxPackets int) (*Stores, error) {
+	ids := make([]C.uint32_t, len(receivers))
+	for i, r := range receivers {
+		ids[i] = C.uint32_t(r)
+	}
+	var p *C.uint32_t
+	if len(ids) > 0 {
+		p = &ids[0]
+	}
+	var h *C.hg_stores
+	rc := C.hg_stores_create(e.ctx, p, C.size_t(len(ids)), C.size_t(maxPackets), &h)
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
+	}
+	return &Stores{e: e, h: h, stride: int(C.hg_packet_stride_words(e.ctx))}, nil
+}
+
+// Close releases the device tables.
+func (s *Stores) Close() {
+	if s.h != nil {
+		C.hg_stores_destroy(s.h)
+		s.h = nil
+	}
+}
+
+// Update replaces the state of the named (receiver, level) pairs, each named
+// at most once: one host-to-device copy and one scatter kernel. Call it after
+// the host store's Store calls of a step with the levels they changed.
+func (s *Stores) Update(ups []StoreUpdate) error {
+	if len(ups) == 0 {
+		return nil
+	}
+	recs := make([]C.hg_store_update, len(ups))
+	var words []uint64
+	for i, u := range ups {
+		recs[i] = C.hg_store_update{receiver: C.uint32_t(u.Receiver), level: C.uint32_t(u.Level)}
+		if u.Best != nil {
+			recs[i].flags = C.HG_STORE_HAS_BEST
+			recs[i].best_off = C.uint32_t(len(words))
+			words = append(words, u.Best...)
+		}
+		recs[i].indiv_off = C.uint32_t(len(words))
+		words = append(words, u.Individuals...)
+	}
+	rc := C.hg_stores_update(s.h, &recs[0], C.size_t(len(recs)), wordPtr(words), C.size_t(len(words)))
+	if rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}
+
+// Read returns one level's device state: the best bitset's words, the
+// verified individual signatures' words, and whether the level has a best.
+func (s *Stores) Read(receiver, level int) (best, individuals []uint64, hasBest bool, err error) {
+	best = make([]uint64, s.stride)
+	individuals = make([]uint64, s.stride)
+	var has C.int
+	rc := C.hg_stores_read(s.h, C.uint32_t(receiver), C.uint32_t(level), wordPtr(best), wordPtr(individuals), &has)
+	if rc != C.HG_OK {
+		return nil, nil, false, s.e.fail(rc)
+	}
+	return best, individuals, has != 0, nil
+}
+
+// Evaluate scores the 2n slots a ParsePackets-shaped parse wrote (slot i:
+// packet i's multisignature, slot n+i: its individual signature; a slot's
+// words at slot*stride): store.go:111-183 against each receiver's store at the
+// packet's level. live (nil, or 2n bytes) is the caller's
+// IndividualSigFilter / rcvCompleted mask. Scores: 0 for a slot whose code is
+// not HG_OK, that is not live, or whose (receiver, level) has no range; -1 for
+// a receiver without a store; else the reference's mark.
+func (s *Stores) Evaluate(recs []C.hg_packet, stride int, words []uint64, codes []int32, live []byte) ([]int32, error) {
+	n := len(recs)
+	if n == 0 {
+		return nil, nil
+	}
+	if len(words) != 2*n*stride || len(codes) != 2*n || (live != nil && len(live) != 2*n) {
+		return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "Evaluate: words, codes and live must cover 2n slots"}
+	}
+	scores := make([]int32, 2*n)
+	rc := C.hg_stores_evaluate(s.h, &recs[0], C.size_t(n), C.size_t(stride), wordPtr(words), codePtr(codes),
+		bytePtr(live), codePtr(scores))
+	if rc != C.HG_OK {
+		return nil, s.e.fail(rc)
+	}
+	return scores, nil
+}
+
+// EvaluateDevice is Evaluate on arrays already in device memory (the outputs
+// of hg_parse_packets_device), asynchronous on stream (nil: the engine's).
+func (s *Stores) EvaluateDevice(dPkts unsafe.Pointer, n, stride int, dWords, dCodes, dLive, dScores,
+	stream unsafe.Pointer) error {
+	rc := C.hg_stores_evaluate_device(s.h, (*C.hg_packet)(dPkts), C.size_t(n), C.size_t(stride),
+		(*C.uint64_t)(dWords), (*C.int32_t)(dCodes), (*C.uint8_t)(dLive), (*C.int32_t)(dScores), stream)
+	if rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}
+
+// SelectCapacity is the number of entries SelectDevice writes for n packets
+// and k picks per store: min(2n, stores*k).
+func (s *Stores) SelectCapacity(n, k int) int {
+	return int(C.hg_stores_select_capacity(s.h, C.size_t(n), C.uint32_t(k)))
+}
+
+// SelectDevice is readTodos with k slots per store (processing.go:171-220) on
+// device arrays: the k best slots of score > 0 per store (ties: a packet's
+// multisignature before its individual signature, earlier packets first),
+// grouped by store, with their requests and signatures gathered into
+// dOutReqs / dOutSigs for hg_verify_aggregate_device. Entries from *dCount to
+// SelectCapacity hold a request that fails the level check, so the whole
+// capacity may be verified without reading the count back.
+func (s *Stores) SelectDevice(dPkts unsafe.Pointer, n int, dScores unsafe.Pointer, k int, dReqs, dSigs, dSel, dCount,
+	dOutReqs, dOutSigs, stream unsafe.Pointer) error {
+	rc := C.hg_stores_select_device(s.h, (*C.hg_packet)(dPkts), C.size_t(n), (*C.int32_t)(dScores), C.uint32_t(k),
+		(*C.hg_request)(dReqs), (*C.uint8_t)(dSigs), (*C.uint32_t)(dSel), (*C.uint32_t)(dCount),
+		(*C.hg_request)(dOutReqs), (*C.uint8_t)(dOutSigs), stream)
+	if rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}

@@ -41,6 +41,7 @@ HG_ERR_PKT_NO_SIG = 27
 HG_ERR_PKT_ID_RANGE = 28
 HG_PKT_NO_IND = 29
 HG_PKT_HAS_IND = 1
+HG_STORE_HAS_BEST = 1
 HG_ERR_ARG = 100
 HG_ERR_DEVICE = 101
 
@@ -104,6 +105,14 @@ SIGNATURES = {
     "hg_parse_packets": (_I, [_P, _P, _SZ, _P, _SZ, _SZ, _P, _P, _P, _P]),
     "hg_parse_packets_device": (_I, [_P, _P, _SZ, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
     "hg_packet_error": (_I, [_P, _I, _P, ctypes.c_char_p, _SZ]),
+    "hg_stores_create": (_I, [_P, _P, _SZ, _SZ, ctypes.POINTER(_P)]),
+    "hg_stores_destroy": (None, [_P]),
+    "hg_stores_update": (_I, [_P, _P, _SZ, _P, _SZ]),
+    "hg_stores_read": (_I, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, ctypes.POINTER(_I)]),
+    "hg_stores_evaluate_device": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    "hg_stores_evaluate": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P]),
+    "hg_stores_select_capacity": (_SZ, [_P, _SZ, ctypes.c_uint32]),
+    "hg_stores_select_device": (_I, [_P, _P, _SZ, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "hg_batcher_create": (_I, [_P, _SZ, ctypes.c_uint, ctypes.POINTER(_P)]),
     "hg_batcher_destroy": (None, [_P]),
     "hg_batcher_submit": (_I, [_P, _P, _SZ, _P, _P, _P, ctypes.POINTER(_P)]),

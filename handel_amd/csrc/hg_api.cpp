@@ -23,6 +23,7 @@
 #include "bn256_kernels.h"
 #include "hg_codes.h"
 #include "hg_packets.h"
+#include "hg_stores.h"
 
 using namespace hg;
 
@@ -232,6 +233,7 @@ struct hg_ctx {
   // registry (nreg > 0 only while every table below matches it)
   DevBuf<PointG2> reg;
   size_t nreg = 0;
+  uint64_t reg_gen = 0;  // counts hg_registry_load calls: a hg_stores belongs to one of them
   // aligned block sums of the registry (level k block j at blocks[block_base[k] + j])
   DevBuf<PointG2> blocks;
   // subset sums of every aligned 8-key window (256 per window), the fold's table
@@ -312,6 +314,54 @@ struct hg_lane {
   DevBuf<uint8_t> d_in;
   DevBuf<int32_t> d_codes;
   size_t n = 0, nwords = 0, off_sigs = 0, off_words = 0, in_bytes = 0;
+};
+
+// Device-resident stores of the Handel instances a process hosts (hg_stores.hip):
+// the tables, the host copy of the receiver map, and the workspaces of the
+// host-pointer evaluate and of the selection, sized at creation.
+struct hg_stores {
+  hg_ctx* c = nullptr;
+  uint64_t reg_gen = 0;  // the registry load it was created on
+  size_t nreg = 0, max_packets = 0;
+  int levels = 0, stride = 0;
+  std::vector<uint32_t> receivers;
+  std::vector<int32_t> map;  // receiver id -> store index, -1
+  DevBuf<uint64_t> tab;
+  DevBuf<uint32_t> flags;
+  DevBuf<int32_t> d_map;
+  // hg_stores_update staging
+  DevBuf<hg_store_update> ups;
+  DevBuf<uint64_t> up_words;
+  // hg_stores_evaluate staging
+  DevBuf<hg_packet> pkts;
+  DevBuf<uint64_t> words;
+  DevBuf<int32_t> codes, scores;
+  DevBuf<uint8_t> live;
+  // selection
+  DevBuf<uint64_t> keys_a, keys_b;
+  DevBuf<uint32_t> cnt, picks, base;
+  DevBuf<uint8_t> temp;
+  StoreTab table() const {
+    return StoreTab{tab.p, flags.p, d_map.p, (uint32_t)nreg, levels, stride, (int)receivers.size()};
+  }
+  void release() {
+    tab.release();
+    flags.release();
+    d_map.release();
+    ups.release();
+    up_words.release();
+    pkts.release();
+    words.release();
+    codes.release();
+    scores.release();
+    live.release();
+    keys_a.release();
+    keys_b.release();
+    cnt.release();
+    picks.release();
+    base.release();
+    temp.release();
+  }
 };
 
 // ---------------------------------------------------------------- submission order
@@ -1155,6 +1205,7 @@ int hg_registry_load(hg_ctx* c, const uint8_t* pks, size_t n, int32_t* codes) {
   // until every table is rebuilt the context has no registry: a failure below
   // leaves it empty (every aggregate request then fails its range check)
   c->nreg = 0;
+  c->reg_gen++;
   c->block_levels = 0;
   c->gt_level = 0;
   c->gt_requests = 0;
@@ -1697,6 +1748,233 @@ int hg_packet_error(hg_ctx* c, int code, const hg_packet* p, char* buf, size_t c
                     hi, (int)p->level);
   }
   return snprintf(buf, cap, "%s", hg_code_string(code, flavor));
+}
+
+// ---------------------------------------------------------------- stores
+// true while the store set's registry is the context's (call with c->mu held)
+static bool stores_current(const hg_stores* st) {
+  return st->reg_gen == st->c->reg_gen && st->nreg == st->c->nreg && st->nreg > 0;
+}
+
+int hg_stores_create(hg_ctx* c, const uint32_t* receivers, size_t n_receivers, size_t max_packets, hg_stores** out) {
+  if (out) *out = nullptr;
+  if (!c || !receivers || !out || n_receivers == 0 || max_packets == 0 || max_packets > kStoreMaxPackets)
+    return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  const size_t nreg = c->nreg;
+  const int levels = pkt_log2_ceil(nreg);
+  if (nreg == 0 || levels < 1 || levels > kStoreMaxLevels || n_receivers > nreg) return HG_ERR_ARG;
+  std::vector<int32_t> map(nreg, -1);
+  for (size_t i = 0; i < n_receivers; i++) {
+    if (receivers[i] >= nreg || map[receivers[i]] >= 0) return HG_ERR_ARG;
+    map[receivers[i]] = (int32_t)i;
+  }
+  HG_CHECK(c, hipSetDevice(c->device));
+  hg_stores* st = new hg_stores();
+  st->c = c;
+  st->reg_gen = c->reg_gen;
+  st->nreg = nreg;
+  st->max_packets = max_packets;
+  st->levels = levels;
+  st->stride = (int)pkt_stride_words(nreg);
+  st->receivers.assign(receivers, receivers + n_receivers);
+  st->map = std::move(map);
+  const size_t rows = n_receivers * (size_t)levels;
+  const size_t n2 = 2 * max_packets;
+  size_t temp_bytes = 0;
+  hipError_t e = store_select_temp_bytes(n2, n_receivers, &temp_bytes);
+  if (e == hipSuccess) e = st->tab.ensure(2 * rows * st->stride);
+  if (e == hipSuccess) e = st->flags.ensure(rows);
+  if (e == hipSuccess) e = st->d_map.ensure(nreg);
+  if (e == hipSuccess) e = st->keys_a.ensure(n2);
+  if (e == hipSuccess) e = st->keys_b.ensure(n2);
+  if (e == hipSuccess) e = st->cnt.ensure(n_receivers + 1);
+  if (e == hipSuccess) e = st->picks.ensure(n_receivers + 1);
+  if (e == hipSuccess) e = st->base.ensure(n_receivers + 1);
+  if (e == hipSuccess) e = st->temp.ensure(temp_bytes ? temp_bytes : 1);
+  Submission sub(c, c->stream);
+  if (e == hipSuccess) e = sub.start();
+  if (e == hipSuccess) e = hipMemsetAsync(st->tab.p, 0, st->tab.cap * sizeof(uint64_t), c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(st->flags.p, 0, st->flags.cap * sizeof(uint32_t), c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(st->d_map.p, st->map.data(), nreg * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    c->err = std::string("hg_stores_create: ") + hipGetErrorString(e);
+    st->release();
+    delete st;
+    return HG_ERR_DEVICE;
+  }
+  *out = st;
+  return HG_OK;
+}
+
+void hg_stores_destroy(hg_stores* st) {
+  if (!st) return;
+  hg_ctx* c = st->c;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    if (c->last_ev) (void)hipEventSynchronize(c->last_ev);  // a submission on a caller stream
+    st->release();
+  }
+  delete st;
+}
+
+int hg_stores_update(hg_stores* st, const hg_store_update* ups, size_t n, const uint64_t* words, size_t nwords) {
+  if (!st || (n && !ups) || (nwords && !words)) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st)) return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  if (n > st->receivers.size() * (size_t)st->levels) return HG_ERR_ARG;  // each (receiver, level) at most once
+  std::vector<bool> seen(st->receivers.size() * (size_t)st->levels, false);
+  for (size_t i = 0; i < n; i++) {
+    const hg_store_update& u = ups[i];
+    uint32_t lo = 0, hi = 0;
+    if (u.receiver >= st->nreg || st->map[u.receiver] < 0 || u.level < 1 || u.level > (uint32_t)st->levels ||
+        !pkt_range_level(u.receiver, (uint32_t)st->nreg, (int)u.level, lo, hi))
+      return HG_ERR_ARG;
+    const size_t nw = ((size_t)(hi - lo) + 63) / 64;
+    if ((uint64_t)u.indiv_off + nw > nwords || ((u.flags & HG_STORE_HAS_BEST) && (uint64_t)u.best_off + nw > nwords))
+      return HG_ERR_ARG;
+    const size_t row = (size_t)st->map[u.receiver] * st->levels + (u.level - 1);
+    if (seen[row]) return HG_ERR_ARG;
+    seen[row] = true;
+  }
+  HG_CHECK(c, hipSetDevice(c->device));
+  HG_CHECK(c, st->ups.ensure(n));
+  HG_CHECK(c, st->up_words.ensure(nwords ? nwords : 1));
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(st->ups.p, ups, n * sizeof(hg_store_update), hipMemcpyHostToDevice, c->stream));
+  if (nwords)
+    HG_CHECK(c, hipMemcpyAsync(st->up_words.p, words, nwords * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  launch_store_update(st->table(), st->ups.p, (int)n, st->up_words.p, c->stream);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+
+int hg_stores_read(hg_stores* st, uint32_t receiver, uint32_t level, uint64_t* best, uint64_t* indiv, int* has_best) {
+  if (!st) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st)) return HG_ERR_ARG;
+  if (receiver >= st->nreg || st->map[receiver] < 0 || level < 1 || level > (uint32_t)st->levels) return HG_ERR_ARG;
+  HG_CHECK(c, hipSetDevice(c->device));
+  const size_t row = (size_t)st->map[receiver] * st->levels + (level - 1);
+  const uint64_t* src = st->tab.p + 2 * row * st->stride;
+  const size_t bytes = (size_t)st->stride * sizeof(uint64_t);
+  uint32_t flags = 0;
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  if (best) HG_CHECK(c, hipMemcpyAsync(best, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (indiv) HG_CHECK(c, hipMemcpyAsync(indiv, src + st->stride, bytes, hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, hipMemcpyAsync(&flags, st->flags.p + row, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  if (has_best) *has_best = (flags & HG_STORE_HAS_BEST) ? 1 : 0;
+  return HG_OK;
+}
+
+// n and the slot stride of an evaluate call against the store set's registry
+static bool stores_slots_ok(const hg_stores* st, size_t n, size_t stride) {
+  return n <= kStoreMaxPackets && stride >= (size_t)st->stride && stride <= (size_t)INT32_MAX &&
+         (n == 0 || 2 * n <= (size_t)UINT32_MAX / stride);
+}
+
+int hg_stores_evaluate_device(hg_stores* st, const hg_packet* d_pkts, size_t n, size_t stride_words,
+                              const uint64_t* d_words, const int32_t* d_codes, const uint8_t* d_live,
+                              int32_t* d_scores, void* stream) {
+  if (!st || (n && (!d_pkts || !d_words || !d_codes || !d_scores))) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !stores_slots_ok(st, n, stride_words)) return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  launch_store_evaluate(st->table(), d_pkts, (int)n, (int)stride_words, d_words, d_codes, d_live, d_scores, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  return HG_OK;
+}
+
+int hg_stores_evaluate(hg_stores* st, const hg_packet* pkts, size_t n, size_t stride_words, const uint64_t* words,
+                       const int32_t* codes, const uint8_t* live, int32_t* scores) {
+  if (!st || (n && (!pkts || !words || !codes || !scores))) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !stores_slots_ok(st, n, stride_words) || n > st->max_packets) return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  const size_t nw = 2 * n * stride_words;
+  HG_CHECK(c, st->pkts.ensure(n));
+  HG_CHECK(c, st->words.ensure(nw));
+  HG_CHECK(c, st->codes.ensure(2 * n));
+  HG_CHECK(c, st->scores.ensure(2 * n));
+  if (live) HG_CHECK(c, st->live.ensure(2 * n));
+  hipStream_t s = c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(st->pkts.p, pkts, n * sizeof(hg_packet), hipMemcpyHostToDevice, s));
+  HG_CHECK(c, hipMemcpyAsync(st->words.p, words, nw * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  HG_CHECK(c, hipMemcpyAsync(st->codes.p, codes, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (live) HG_CHECK(c, hipMemcpyAsync(st->live.p, live, 2 * n, hipMemcpyHostToDevice, s));
+  launch_store_evaluate(st->table(), st->pkts.p, (int)n, (int)stride_words, st->words.p, st->codes.p,
+                        live ? st->live.p : nullptr, st->scores.p, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(scores, st->scores.p, 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(s));
+  return HG_OK;
+}
+
+size_t hg_stores_select_capacity(hg_stores* st, size_t n, uint32_t k) {
+  if (!st) return 0;
+  const size_t S = st->receivers.size();  // fixed at creation
+  const size_t n2 = 2 * n;
+  return k == 0 ? 0 : (n2 / k < S ? n2 : S * (size_t)k);
+}
+
+int hg_stores_select_device(hg_stores* st, const hg_packet* d_pkts, size_t n, const int32_t* d_scores, uint32_t k,
+                            const hg_request* d_reqs, const uint8_t* d_sigs, uint32_t* d_sel, uint32_t* d_count,
+                            hg_request* d_out_reqs, uint8_t* d_out_sigs, void* stream) {
+  if (!st || !d_count || k == 0 || (n && (!d_pkts || !d_scores || !d_reqs || !d_sigs || !d_sel || !d_out_reqs || !d_out_sigs)))
+    return HG_ERR_ARG;
+  if (((uintptr_t)d_sigs | (uintptr_t)d_out_sigs) & 3) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || n > st->max_packets) return HG_ERR_ARG;
+  HG_CHECK(c, hipSetDevice(c->device));
+  if (n) {  // the workspace was sized for max_packets; a smaller batch never needs more
+    size_t need = 0;
+    HG_CHECK(c, store_select_temp_bytes(2 * n, st->receivers.size(), &need));
+    if (need > st->temp.cap) {
+      c->err = "hg_stores_select_device: selection workspace too small";
+      return HG_ERR_DEVICE;
+    }
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  if (n == 0) {
+    HG_CHECK(c, hipMemsetAsync(d_count, 0, sizeof(uint32_t), s));
+  } else {
+    const StoreSelectWs ws{st->keys_a.p, st->keys_b.p, st->cnt.p, st->picks.p, st->base.p, st->temp.p, st->temp.cap};
+    const size_t cap = hg_stores_select_capacity(st, n, k);
+    HG_CHECK(c, launch_store_select(st->table(), ws, d_pkts, (int)n, d_scores, k, d_reqs, d_sigs, d_sel, d_count,
+                                    d_out_reqs, d_out_sigs, (uint32_t)cap, s));
+  }
+  HG_CHECK(c, sub.finish());
+  return HG_OK;
 }
 
 size_t hg_context_bytes(hg_ctx* c) {

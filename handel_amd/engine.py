@@ -10,6 +10,7 @@ torch tensors) and a HIP stream handle.
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -24,6 +25,9 @@ REQ_DTYPE = np.dtype([("offset", "<u4"), ("bitlen", "<u4"), ("level_size", "<u4"
 # hg_packet (include/handel_gpu.h): one received Handel packet, marshals as pool ranges
 PACKET_DTYPE = np.dtype([("origin", "<i4"), ("receiver", "<u4"), ("level", "<u4"), ("flags", "<u4"),
                          ("ms_off", "<u4"), ("ms_len", "<u4"), ("ind_off", "<u4"), ("ind_len", "<u4")])
+# hg_store_update (include/handel_gpu.h): one (receiver, level) state pushed to the device stores
+STORE_UPDATE_DTYPE = np.dtype([("receiver", "<u4"), ("level", "<u4"), ("flags", "<u4"), ("best_off", "<u4"),
+                               ("indiv_off", "<u4")])
 
 
 def _ptr(a) -> Optional[int]:
@@ -56,6 +60,10 @@ class Engine:
 
     def close(self):
         if getattr(self, "ctx", None):
+            for ref in getattr(self, "_stores", []):  # device stores go before their context
+                st = ref()
+                if st is not None:
+                    st.close()
             self.L.hg_destroy(self.ctx)
             self.ctx = None
 
@@ -428,6 +436,92 @@ class Batcher:
         b, r = ctypes.c_uint64(), ctypes.c_uint64()
         self.L.hg_batcher_stats(self.b, ctypes.byref(b), ctypes.byref(r))
         return b.value, r.value
+
+
+class Stores:
+    """The device-resident stores of the Handel instances `receivers` on one
+    engine (hg_stores_*): per receiver and level the best bitset, whether there
+    is one, and the verified individual signatures. Scores parsed packet slots
+    (store.go:111-183) and picks the k best per store (processing.go:171-220).
+    The engine must outlive the stores; they die with the registry they were
+    created on."""
+
+    def __init__(self, engine: Engine, receivers, max_packets: int):
+        self.engine = engine
+        self.L = engine.L
+        self.receivers = np.ascontiguousarray(receivers, dtype=np.uint32)
+        self.max_packets = int(max_packets)
+        self.stride = engine.packet_stride_words()
+        h = ctypes.c_void_p()
+        rc = self.L.hg_stores_create(engine.ctx, _ptr(self.receivers) if len(self.receivers) else None,
+                                     len(self.receivers), self.max_packets, ctypes.byref(h))
+        if rc != 0:
+            raise HandelGPUError(f"hg_stores_create: code {rc}")
+        self.h = h
+        engine.__dict__.setdefault("_stores", []).append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hg_stores_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, ups: np.ndarray, words: np.ndarray) -> None:
+        """Replaces the state of the named (receiver, level) pairs (hg_stores_update)."""
+        ups = np.ascontiguousarray(ups, dtype=STORE_UPDATE_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        self.engine._check(self.L.hg_stores_update(self.h, _ptr(ups) if len(ups) else None, len(ups),
+                                                   _ptr(words) if len(words) else None, len(words)),
+                           "hg_stores_update")
+
+    def read(self, receiver: int, level: int) -> Tuple[np.ndarray, np.ndarray, bool]:
+        """(best words, verified-individual words, has best) of one level (hg_stores_read)."""
+        best = np.zeros(self.stride, dtype=np.uint64)
+        indiv = np.zeros(self.stride, dtype=np.uint64)
+        has = ctypes.c_int()
+        self.engine._check(self.L.hg_stores_read(self.h, int(receiver), int(level), _ptr(best), _ptr(indiv),
+                                                 ctypes.byref(has)), "hg_stores_read")
+        return best, indiv, bool(has.value)
+
+    def evaluate(self, pkts: np.ndarray, words: np.ndarray, codes: np.ndarray, live=None,
+                 stride: Optional[int] = None) -> np.ndarray:
+        """Scores of the 2n slots hg_parse_packets wrote (hg_stores_evaluate)."""
+        pkts = np.ascontiguousarray(pkts, dtype=PACKET_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        live = None if live is None else np.ascontiguousarray(live, dtype=np.uint8)
+        n = len(pkts)
+        stride = self.stride if stride is None else int(stride)
+        if len(words) != 2 * n * stride or len(codes) != 2 * n or (live is not None and len(live) != 2 * n):
+            raise ValueError("words, codes and live must cover 2n slots")
+        scores = np.zeros(2 * n, dtype=np.int32)
+        if n:
+            self.engine._check(self.L.hg_stores_evaluate(self.h, _ptr(pkts), n, stride, _ptr(words), _ptr(codes),
+                                                         _ptr(live), _ptr(scores)), "hg_stores_evaluate")
+        return scores
+
+    def evaluate_device(self, d_pkts: int, n: int, stride: int, d_words: int, d_codes: int, d_live: int,
+                        d_scores: int, stream: int = 0) -> None:
+        """hg_stores_evaluate_device on raw device pointers (asynchronous)."""
+        self.engine._check(self.L.hg_stores_evaluate_device(self.h, d_pkts, n, stride, d_words, d_codes,
+                                                            d_live or None, d_scores, stream or None),
+                           "hg_stores_evaluate_device")
+
+    def select_capacity(self, n: int, k: int) -> int:
+        return int(self.L.hg_stores_select_capacity(self.h, int(n), int(k)))
+
+    def select_device(self, d_pkts: int, n: int, d_scores: int, k: int, d_reqs: int, d_sigs: int, d_sel: int,
+                      d_count: int, d_out_reqs: int, d_out_sigs: int, stream: int = 0) -> None:
+        """hg_stores_select_device on raw device pointers (asynchronous): the k
+        best slots per store, gathered into verification requests."""
+        self.engine._check(self.L.hg_stores_select_device(self.h, d_pkts, n, d_scores, int(k), d_reqs, d_sigs, d_sel,
+                                                          d_count, d_out_reqs, d_out_sigs, stream or None),
+                           "hg_stores_select_device")
 
 
 class DeviceLane:

@@ -1,0 +1,236 @@
+"""Packet intake with the scoring step on the GPU: parse -> evaluate -> select
+-> verify over arrays that stay in HBM.
+
+Handel scores every queued signature against its store and verifies only the
+best (processing.go:171-220 readTodos over store.go:101-183 Evaluate).
+`DeviceStores` keeps the scoring state of the hosted Handel instances on the
+device (hg_stores_*); the host `sigprocessing.Store` stays authoritative:
+`Store.store` / unsafeCheckMerge run on the host once per verified signature
+and `mirror` pushes the levels that changed. `DeviceIntake` is one intake step
+for a batch of raw packets of several instances.
+
+`select_reference` / `select_slots` restate the selection rule on plain
+integers (the picks and the order the rest goes back to the queue in); they
+are what the device selection is tested against and what `DeviceIntake` orders
+its pending queue with.
+"""
+
+from __future__ import annotations
+
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import partitioner as part
+from ._lib import HG_OK, HG_STORE_HAS_BEST, HandelGPUError
+from .engine import REQ_DTYPE, STORE_UPDATE_DTYPE, Engine, Stores
+from .packets import Packet, pack_packets
+from .sigprocessing import IncomingSig, IndividualSigFilter, MultiSig, Store, bits_to_int, int_to_words
+
+
+def queue_position(slot: int, n: int) -> int:
+    """Handel's queue order of the 2n slots of a parsed batch: packet index
+    first, a packet's multisignature (slot i) before its individual signature
+    (slot n + i) (handel.go:145-149)."""
+    return 2 * (slot % n) + (1 if slot >= n else 0)
+
+
+def select_reference(marks: Sequence[int], k: int) -> Tuple[List[int], List[int]]:
+    """BatchedEvaluatorProcessing.read_todos on bare marks given in queue
+    order: (indices picked, best first; indices with a positive mark that go
+    back to the queue, in the order read_todos re-queues them)."""
+    slots: List[Tuple[int, int]] = []
+    requeued: List[int] = []
+    for idx, mark in enumerate(marks):
+        if mark <= 0:
+            continue
+        if len(slots) == k and mark <= slots[-1][0]:
+            requeued.append(idx)
+            continue
+        if len(slots) == k:
+            requeued.append(slots.pop()[1])
+        j = len(slots)
+        while j > 0 and slots[j - 1][0] < mark:
+            j -= 1
+        slots.insert(j, (mark, idx))
+    return [i for _, i in slots], requeued
+
+
+def select_slots(store_of_slot: Sequence[int], scores: Sequence[int], n: int, k: int,
+                 n_stores: int) -> Tuple[List[int], List[int]]:
+    """hg_stores_select_device's contract on the host: the picked slots grouped
+    by store (in store order; inside a store by score descending, then queue
+    position), and the slots of positive score that were not picked, per store
+    in read_todos' re-queue order. store_of_slot[slot] < 0: no store."""
+    per_store: List[List[int]] = [[] for _ in range(n_stores)]
+    for slot in sorted(range(2 * n), key=lambda s: queue_position(s, n)):
+        st = int(store_of_slot[slot])
+        if 0 <= st < n_stores:
+            per_store[st].append(slot)
+    picked: List[int] = []
+    rest: List[int] = []
+    for slots in per_store:
+        p, r = select_reference([int(scores[s]) for s in slots], k)
+        picked += [slots[i] for i in p]
+        rest += [slots[i] for i in r]
+    return picked, rest
+
+
+class DeviceStores(Stores):
+    """hg_stores of the receivers a process hosts, fed from host `Store`s."""
+
+    def __init__(self, engine: Engine, receivers: Sequence[int], max_packets: int, n_registry: Optional[int] = None):
+        super().__init__(engine, receivers, max_packets)
+        self.n = int(engine.L.hg_registry_size(engine.ctx)) if n_registry is None else int(n_registry)
+
+    def mirror(self, receiver: int, store: Store, levels: Optional[Iterable[int]] = None) -> None:
+        """Pushes `store`'s state of `levels` (default: every level) to the
+        device store of `receiver`: the best bitset, whether there is one, and
+        the verified individual signatures."""
+        self.mirror_many([(receiver, store, levels)])
+
+    def mirror_many(self, items: Sequence[Tuple[int, Store, Optional[Iterable[int]]]]) -> None:
+        """`mirror` for several stores in one hg_stores_update."""
+        ups, words, nw = [], [], 0
+        for receiver, store, levels in items:
+            for level in (store.levels if levels is None else sorted(set(levels))):
+                size = store.size(level)
+                if size <= 0:
+                    continue
+                with store.lock:
+                    best = store.m.get(level)
+                    indiv = store.indiv_verified.get(level, 0)
+                lw = (size + 63) // 64
+                best_off = nw
+                if best is not None:
+                    words.append(int_to_words(best.bits, size))
+                    nw += lw
+                words.append(int_to_words(indiv, size))
+                ups.append((receiver, level, HG_STORE_HAS_BEST if best is not None else 0, best_off, nw))
+                nw += lw
+        if ups:
+            self.update(np.array(ups, dtype=STORE_UPDATE_DTYPE), np.concatenate(words))
+
+
+class DeviceIntake:
+    """One intake step for raw packets of the hosted receivers: pack -> upload
+    -> hg_parse_packets_device -> hg_stores_evaluate_device ->
+    hg_stores_select_device (k per receiver) -> hg_verify_aggregate_device,
+    every array staying in HBM; only the pick count, the picks, their verdicts
+    and the 2n scores and parse codes come back. The valid picks then go
+    through the host `Store.store` (merges through `Engine.combine_g1`) in
+    selection order, and the levels that changed are pushed back to the
+    device. The engine needs its registry and message set.
+
+    Slots of positive score that were not picked stay queued here and are
+    presented again, in read_todos' order, in front of the next step's packets
+    (each as an entry of its own whose packet is parsed again; a pool of parsed
+    slots kept in HBM across steps is not part of this). Each receiver has the reference's
+    IndividualSigFilter (processing.go:299-325): an origin's individual
+    signature is presented once."""
+
+    def __init__(self, engine: Engine, receivers: Sequence[int], k: int, max_packets: int = 4096,
+                 combine: Optional[Callable[[bytes, bytes], bytes]] = None):
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        self.engine, self.k, self.max_packets = engine, int(k), int(max_packets)
+        self.receivers = [int(r) for r in receivers]
+        self.n = int(engine.L.hg_registry_size(engine.ctx))
+        self.stores = DeviceStores(engine, self.receivers, self.max_packets, self.n)
+        self.stride = self.stores.stride
+        combine = combine or (lambda a, b: engine.combine_g1(a, b)[0])
+        self.host: Dict[int, Store] = {r: Store(r, self.n, combine) for r in self.receivers}
+        self.filters: Dict[int, IndividualSigFilter] = {r: IndividualSigFilter() for r in self.receivers}
+        self.index = {r: i for i, r in enumerate(self.receivers)}
+        # (packet, receiver, multisignature still queued, individual signature still queued)
+        self.pending: List[Tuple[Packet, int, bool, bool]] = []
+
+    def close(self):
+        self.stores.close()
+
+    def _incoming(self, pkt: Packet, receiver: int, individual: bool) -> IncomingSig:
+        lo, hi = part.range_level(receiver, self.n, pkt.level)
+        if individual:
+            ms = MultiSig(hi - lo, 1 << (pkt.origin - lo), bytes(pkt.individual[:64]))
+            return IncomingSig(pkt.origin, pkt.level, ms, ind=True, mapped_index=pkt.origin - lo)
+        bits, sig = part.multisig_unmarshal(pkt.multisig)
+        return IncomingSig(pkt.origin, pkt.level, MultiSig(len(bits), bits_to_int(bits), bytes(sig[:64])))
+
+    def step(self, packets: Sequence[Packet], receivers: Sequence[int]):
+        """Returns (results, unselected): results holds (receiver, IncomingSig,
+        error text or None) per picked slot in selection order; unselected the
+        slots of positive score that were not picked (indices into this step's
+        2n slots, queued slots first), which stay queued for the next step."""
+        import torch
+
+        if len(packets) != len(receivers):
+            raise ValueError("one receiver per packet")
+        batch = list(self.pending) + [(p, int(r), True, p.individual is not None) for p, r in zip(packets, receivers)]
+        n, n_old = len(batch), len(self.pending)
+        if n == 0:
+            return [], []
+        if n > self.max_packets:
+            raise ValueError(f"{n} packets (queued ones included) exceed max_packets = {self.max_packets}")
+        live = np.zeros(2 * n, dtype=np.uint8)
+        fresh_ind = []  # new packets whose individual signature passed the filter now
+        for i, (p, r, want_ms, want_ind) in enumerate(batch):
+            live[i] = want_ms
+            if i >= n_old and want_ind and r in self.filters:
+                # the filter sees a signature once its packet parsed (handel.go:127-152): undone below if it did not
+                want_ind = self.filters[r].accept(IncomingSig(p.origin, p.level, None, ind=True))
+                if want_ind:
+                    fresh_ind.append(i)
+            live[n + i] = want_ind
+        pool, recs = pack_packets([b[0] for b in batch], [b[1] for b in batch])
+        eng, st, stride = self.engine, self.stores, self.stride
+        dev = torch.device("cuda", eng.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
+        d_pool, d_pkts, d_live = up(np.frombuffer(pool, dtype=np.uint8)), up(recs), up(live)
+        cap = st.select_capacity(n, self.k)
+        d_reqs = torch.empty(2 * n * REQ_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_words = torch.empty(2 * n * stride, dtype=torch.int64, device=dev)
+        d_sigs = torch.empty(2 * n * 64, dtype=torch.uint8, device=dev)
+        d_pcodes = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        d_scores = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        d_sel = torch.empty(cap, dtype=torch.int32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_oreqs = torch.empty(cap * REQ_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_osigs = torch.empty(cap * 64, dtype=torch.uint8, device=dev)
+        d_vcodes = torch.empty(cap, dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        eng.parse_packets_device(d_pool.data_ptr(), len(pool), d_pkts.data_ptr(), n, stride, d_reqs.data_ptr(),
+                                 d_words.data_ptr(), d_sigs.data_ptr(), d_pcodes.data_ptr(), s)
+        st.evaluate_device(d_pkts.data_ptr(), n, stride, d_words.data_ptr(), d_pcodes.data_ptr(), d_live.data_ptr(),
+                           d_scores.data_ptr(), s)
+        st.select_device(d_pkts.data_ptr(), n, d_scores.data_ptr(), self.k, d_reqs.data_ptr(), d_sigs.data_ptr(),
+                         d_sel.data_ptr(), d_count.data_ptr(), d_oreqs.data_ptr(), d_osigs.data_ptr(), s)
+        # the whole capacity without reading the count first: the filler fails the level check
+        eng.verify_aggregate_device(d_oreqs.data_ptr(), cap, d_words.data_ptr(), d_osigs.data_ptr(),
+                                    d_vcodes.data_ptr(), stream=s)
+        torch.cuda.synchronize(dev)
+        count = int(d_count.cpu().numpy()[0])
+        sel = d_sel.cpu().numpy()[:count].astype(np.int64)
+        vcodes = d_vcodes.cpu().numpy()[:count]
+        scores = d_scores.cpu().numpy()
+        pcodes = d_pcodes.cpu().numpy()
+        for i in fresh_ind:  # a packet that failed to parse never reached the filter
+            if pcodes[i] != HG_OK:
+                self.filters[batch[i][1]].seen.pop(batch[i][0].origin, None)
+        results, changed = [], {}
+        for slot, code in zip(sel.tolist(), vcodes.tolist()):
+            p, r = batch[slot % n][0], batch[slot % n][1]
+            sp = self._incoming(p, r, slot >= n)
+            err = None if code == HG_OK else eng.processing_error_string(int(code))
+            if err is None:
+                self.host[r].store(sp)
+                changed.setdefault(r, set()).add(sp.level)
+            results.append((r, sp, err))
+        if changed:
+            st.mirror_many([(r, self.host[r], lv) for r, lv in changed.items()])
+        store_of_slot = [self.index.get(batch[slot % n][1], -1) for slot in range(2 * n)]
+        picked, rest = select_slots(store_of_slot, scores, n, self.k, len(self.receivers))
+        if picked != sel.tolist():
+            raise HandelGPUError("device selection differs from read_todos' rule")
+        # the queue of the next step: one entry per waiting slot, in read_todos' order
+        self.pending = [(batch[slot % n][0], batch[slot % n][1], slot < n, slot >= n) for slot in rest]
+        return results, rest

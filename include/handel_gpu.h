@@ -341,6 +341,84 @@ int hg_parse_packets_device(hg_ctx* ctx, const uint8_t* d_pool, size_t pool_len,
  * full length (snprintf convention). */
 int hg_packet_error(hg_ctx* ctx, int code, const hg_packet* p, char* buf, size_t cap);
 
+/* ---------------------------------------------------------------- stores
+ * The scoring step between parse and verify (processing.go:171-220 readTodos
+ * over store.go:101-183 Evaluate), on the device. One hg_stores holds, for
+ * every Handel instance (receiver) the process hosts and every level
+ * 1..ceil(log2 N), the level's best bitset, whether there is one, and the
+ * bitset of verified individual signatures (store.go:39-80), each
+ * hg_packet_stride_words words, the two bitsets of a level adjacent. The host
+ * store stays authoritative: Store / unsafeCheckMerge (store.go:82-226) run on
+ * the host once per verified signature, and the levels that changed are pushed
+ * with hg_stores_update; only the scoring of queued signatures runs here.
+ * A store set belongs to the registry its context held at hg_stores_create:
+ * after a later hg_registry_load every call returns HG_ERR_ARG. Every call
+ * is a submission of the context (ordered with parse and verify across
+ * streams). Destroy the stores before their context. Registries of at most
+ * 2^17 keys (a level's bit length is 16 bits on the wire). */
+typedef struct hg_stores hg_stores;
+typedef struct {
+  uint32_t receiver; /* a hosted receiver id */
+  uint32_t level;    /* one of the receiver's non-empty levels */
+  uint32_t flags;    /* HG_STORE_HAS_BEST: the level has a best multisignature */
+  uint32_t best_off, indiv_off; /* ceil(level size / 64) words each at words[off ...]; best_off unused without HAS_BEST */
+} hg_store_update;
+#define HG_STORE_HAS_BEST 1u
+/* receivers: n_receivers >= 1 distinct ids below the registry size (else
+ * HG_ERR_ARG); store index i = receivers[i]. max_packets >= 1 sizes the
+ * workspaces of hg_stores_evaluate and hg_stores_select_device. Every level
+ * starts without a best and without individual signatures. */
+int hg_stores_create(hg_ctx* ctx, const uint32_t* receivers, size_t n_receivers, size_t max_packets, hg_stores** out);
+void hg_stores_destroy(hg_stores* st);
+/* Replaces the state of n (receiver, level) pairs, each named at most once:
+ * one host-to-device copy and one scatter kernel. Bits at or above the
+ * level's size are cleared on the way in. Synchronous (the inputs are free
+ * on return). */
+int hg_stores_update(hg_stores* st, const hg_store_update* ups, size_t n, const uint64_t* words, size_t nwords);
+/* Reads one level back: best and indiv receive hg_packet_stride_words words
+ * each (nullable), *has_best 0 or 1 (nullable). */
+int hg_stores_read(hg_stores* st, uint32_t receiver, uint32_t level, uint64_t* best, uint64_t* indiv, int* has_best);
+/* store.go:111-183 unsafeEvaluate for the 2n slots hg_parse_packets* wrote
+ * (slot i: packet i's multisignature, slot n + i: its individual signature;
+ * a slot's words at slot * stride_words; d_reqs is not needed: the level
+ * range is recomputed from the packet's receiver and level). d_scores[slot]:
+ *   0  when d_codes[slot] != HG_OK (HG_PKT_NO_IND included), when d_live
+ *      (nullable, 2n bytes: the caller's IndividualSigFilter / rcvCompleted
+ *      mask) holds 0 for the slot, or when the packet's (receiver, level) has
+ *      no range, in this order; nothing else is read for such a slot;
+ *   -1 when the receiver has no store (Handel's marks are never negative);
+ *   else the reference's mark against the receiver's store at the packet's
+ *   level: 0 for a completed level, a verified individual signature or a
+ *   multisignature the best already covers, 1 for an individual signature
+ *   that adds nothing, 1000000 - 10*level - combineCt when the level
+ *   completes, else 100000 - 100*level + 10*addedSigs - combineCt.
+ * stride_words >= hg_packet_stride_words. Asynchronous on `stream`. */
+int hg_stores_evaluate_device(hg_stores* st, const hg_packet* d_pkts, size_t n, size_t stride_words,
+                              const uint64_t* d_words, const int32_t* d_codes, const uint8_t* d_live,
+                              int32_t* d_scores, void* stream);
+/* The same with host pointers (n <= max_packets; words: 2n * stride_words). */
+int hg_stores_evaluate(hg_stores* st, const hg_packet* pkts, size_t n, size_t stride_words, const uint64_t* words,
+                       const int32_t* codes, const uint8_t* live, int32_t* scores);
+/* Entries hg_stores_select_device writes: min(2n, n_receivers * k). */
+size_t hg_stores_select_capacity(hg_stores* st, size_t n, uint32_t k);
+/* readTodos with k slots per store (processing.go:171-220): per store the at
+ * most k slots of score > 0 with the highest scores, among equal scores the
+ * earliest in Handel's queue order, position 2*(slot mod n) + (slot >= n)
+ * (a packet's multisignature before its individual signature, handel.go:
+ * 145-149). Output grouped by store in creation order, inside a store by
+ * score descending then position; the same input gives the same output.
+ * d_sel[0 .. *d_count): the chosen slots; d_out_reqs / d_out_sigs: their
+ * requests (word_offset untouched: they still point into the parsed words)
+ * and 64-byte signatures, contiguous. Entries [*d_count, capacity) hold
+ * 0xffffffff, a request that fails the level check (bitlen 0, level_size 1)
+ * and a zero signature, so a caller may submit `capacity` requests to
+ * hg_verify_aggregate_device without reading the count back. n <=
+ * max_packets, k >= 1; d_sigs and d_out_sigs 4-byte aligned. Asynchronous on
+ * `stream`. */
+int hg_stores_select_device(hg_stores* st, const hg_packet* d_pkts, size_t n, const int32_t* d_scores, uint32_t k,
+                            const hg_request* d_reqs, const uint8_t* d_sigs, uint32_t* d_sel, uint32_t* d_count,
+                            hg_request* d_out_reqs, uint8_t* d_out_sigs, void* stream);
+
 /* ---------------------------------------------------------------- batcher
  * A launch-merging request queue on one context, for callers that verify one
  * multisignature at a time: each Handel instance's processLoop checks one
