@@ -20,7 +20,9 @@
 // generator bounds every limb sum below 2^32, every 64-bit column below 2^64
 // and the REDC result: below 2p for product-only rounds (acc_reduce: one
 // conditional subtraction), below 31p with linear terms (acc_reduce_wide,
-// or its lazy form: the quotient estimate alone, [0, 2p)).
+// or its lazy form: the quotient estimate alone, [0, 2p)). The 12-lane
+// pairing programs' linear-term rounds carry their own bound QMAX and reduce
+// in one carry chain (XQ<QMAX>::x_round, bn256_redq.h).
 //
 // Every table is bound to one call site: operands are absolute positions in
 // the team region (Fp12 slot s element e -> element 12 s + e, register r ->
@@ -28,6 +30,7 @@
 #pragma once
 #include <utility>
 
+#include "bn256_redq.h"
 #include "bn256_team.h"
 
 namespace hg {
@@ -46,7 +49,15 @@ struct XStream;
 template <int NV, int NT, int NP, int NL, int W, int NP2, int NL2, int KP, int KL1, int KL2, int KS1, int KS2, int LZ,
           int EF, int FU>
 HG_DEV void x_round(const Team& T, XStream& S, int off, XHint nxt);
-
+// x_round with the one-chain reduction tail (bn256_redq.h) for its linear-term
+// job: QM is the round's quotient bound from the generator, REDC result below
+// (QM + 1) p. Plain x_round keeps acc_reduce_wide (the 16-lane programs).
+template <int QM>
+struct XQ {
+  template <int NV, int NT, int NP, int NL, int W, int NP2, int NL2, int KP, int KL1, int KL2, int KS1, int KS2,
+            int LZ, int EF, int FU>
+  HG_DEV static void x_round(const Team& T, XStream& S, int off, XHint nxt);
+};
 
 }  // namespace hg
 
@@ -279,9 +290,20 @@ HG_DEV void x_products_ks(const Team& T, const uint32_t (&w)[W], int base, Acc& 
   if constexpr (FUSE) acc_mad_redc(acc, a, b);  // a, b: the last product's operands
 }
 
+// the job's reduction; QM > 0: linear terms in one carry chain (bn256_redq.h)
+template <int FROM, int NL, int LZ, int QM>
+HG_DEV void x_reduce(Fp& r, Acc& acc) {
+  if constexpr (NL > 0 && QM > 0) {
+    acc_redc_digits<FROM>(acc);
+    redq_tail<QM, LZ != 0>(r.l, acc.c + kRedcSteps);
+  } else if constexpr (NL > 0 && LZ) acc_reduce_wide_lazy<FROM>(r, acc);  // linear terms, lazy: [0, 2p)
+  else if constexpr (NL > 0) acc_reduce_wide<FROM>(r, acc);              // linear terms: result < 31p
+  else acc_reduce<FROM>(r, acc);                                         // products only: < 2p, one subtraction
+}
+
 // EF: a0, b0 already hold the first product's operands (read before the
 // pre-pass: plain elements, see x_round)
-template <int W, int NP, int NL, int KL, int KS, int LZ = 0, int EF = 0, int FU = 0>
+template <int W, int NP, int NL, int KL, int KS, int LZ = 0, int EF = 0, int FU = 0, int QM = 0>
 HG_DEV void x_job(const Team& T, const uint32_t (&w)[W], int base, Fp& r, uint32_t& dst, Fp a0 = Fp{},
                   Fp b0 = Fp{}) {
   Acc acc;
@@ -306,9 +328,7 @@ HG_DEV void x_job(const Team& T, const uint32_t (&w)[W], int base, Fp& r, uint32
   if constexpr (KS) x_products_ks<W, NP, FUSE>(T, w, base, acc, a0, b0);
   else x_products<W, NP, FUSE>(T, w, base, acc, a0, b0);
   dst = x_off(w, base + lbase + NL);
-  if constexpr (NL > 0 && LZ) acc_reduce_wide_lazy<FROM>(r, acc);  // linear terms, lazy: [0, 2p)
-  else if constexpr (NL > 0) acc_reduce_wide<FROM>(r, acc);       // linear terms: result < 31p
-  else acc_reduce<FROM>(r, acc);                                  // products only: < 2p, one subtraction
+  x_reduce<FROM, NL, LZ, QM>(r, acc);
 }
 
 // A single-job round on a team spread over the kSplitWaves waves of a
@@ -325,7 +345,7 @@ struct XSplitRange {
   static constexpr int kHi = (R + 1) * kQ < NP ? (R + 1) * kQ : NP;
   static constexpr int kN = kHi - kLo;
 };
-template <int W, int NP, int NL, int KL, int KS, int LZ, int EF>
+template <int W, int NP, int NL, int KL, int KS, int LZ, int EF, int QM>
 HG_DEV void x_job_split(const Team& T, const uint32_t (&w)[W], int base, Fp a0, Fp b0) {
   constexpr int lbase = 2 * NP;
   constexpr int H = XSplitRange<NP, 0>::kN;  // wave 0's products
@@ -405,9 +425,7 @@ HG_DEV void x_job_split(const Team& T, const uint32_t (&w)[W], int base, Fp a0, 
 #pragma unroll
   for (int l = 0; l < 10; l++) r.l[l] = (uint32_t)acc.c[11 + l] & kMask;
 #else
-  if constexpr (NL > 0 && LZ) acc_reduce_wide_lazy<0>(r, acc);
-  else if constexpr (NL > 0) acc_reduce_wide<0>(r, acc);
-  else acc_reduce<0>(r, acc);
+  x_reduce<0, NL, LZ, QM>(r, acc);
 #endif
   if (dst != 0xffffu) st_fp_a8(x_at(T, dst), r.l);
   __syncthreads();  // the round's end
@@ -461,10 +479,10 @@ HG_DEV void x_prepass_split(const Team& T, const uint32_t (&w)[W]) {
 // then job 1 (NP x (u, v), NL x term, dst) and, in a fused round (NP2 + NL2 >
 // 0), job 2 (NP2 x (u, v), NL2 x term, dst2); padded to W dwords. Both jobs
 // read before either result is stored, so in-place programs are fine.
-// off: the round's table offset
-template <int NV, int NT, int NP, int NL, int W, int NP2, int NL2, int KP, int KL1, int KL2, int KS1, int KS2, int LZ,
-          int EF, int FU>
-HG_DEV void x_round(const Team& T, XStream& S, int off, XHint nxt) {
+// off: the round's table offset; QM: see XQ
+template <int QM, int NV, int NT, int NP, int NL, int W, int NP2, int NL2, int KP, int KL1, int KL2, int KS1, int KS2,
+          int LZ, int EF, int FU>
+HG_DEV void x_round_q(const Team& T, XStream& S, int off, XHint nxt) {
   if (S.off != off) x_fetch(T, S, XHint{off, W});  // wave-uniform; only without a (correct) hint
   uint32_t w[W];
   x_for<W>([&](auto i) { w[i] = S.w[i]; });
@@ -508,14 +526,14 @@ HG_DEV void x_round(const Team& T, XStream& S, int off, XHint nxt) {
   }
   if constexpr (kTeamSplit && NP2 == 0 && NL2 == 0) {
     if (T.split) {
-      x_job_split<W, NP, NL, KL1, KS1, LZ, EF>(T, w, jbase, e0, e1);
+      x_job_split<W, NP, NL, KL1, KS1, LZ, EF, QM>(T, w, jbase, e0, e1);
       return;
     }
   }
   Fp r;
   uint32_t dst;
-  if constexpr (EF) x_job<W, NP, NL, KL1, KS1, LZ, EF, FU>(T, w, jbase, r, dst, e0, e1);
-  else x_job<W, NP, NL, KL1, KS1, LZ, 0, FU>(T, w, jbase, r, dst);
+  if constexpr (EF) x_job<W, NP, NL, KL1, KS1, LZ, EF, FU, QM>(T, w, jbase, r, dst, e0, e1);
+  else x_job<W, NP, NL, KL1, KS1, LZ, 0, FU, QM>(T, w, jbase, r, dst);
   if constexpr (NP2 > 0 || NL2 > 0) {
     Fp r2;
     uint32_t dst2;
@@ -531,6 +549,19 @@ HG_DEV void x_round(const Team& T, XStream& S, int off, XHint nxt) {
     if (dst != 0xffffu) st_fp_a8(x_at(T, dst), r.l);
   }
   team_sync(T);
+}
+
+template <int NV, int NT, int NP, int NL, int W, int NP2, int NL2, int KP, int KL1, int KL2, int KS1, int KS2, int LZ,
+          int EF, int FU>
+HG_DEV void x_round(const Team& T, XStream& S, int off, XHint nxt) {
+  x_round_q<0, NV, NT, NP, NL, W, NP2, NL2, KP, KL1, KL2, KS1, KS2, LZ, EF, FU>(T, S, off, nxt);
+}
+template <int QM>
+template <int NV, int NT, int NP, int NL, int W, int NP2, int NL2, int KP, int KL1, int KL2, int KS1, int KS2, int LZ,
+          int EF, int FU>
+HG_DEV void XQ<QM>::x_round(const Team& T, XStream& S, int off, XHint nxt) {
+  static_assert(NL > 0 && NP2 == 0 && NL2 == 0, "one-chain rounds: one job with linear terms");
+  x_round_q<QM, NV, NT, NP, NL, W, NP2, NL2, KP, KL1, KL2, KS1, KS2, LZ, EF, FU>(T, S, off, nxt);
 }
 
 // ------------------------------------------------------------------ call-site wrappers

@@ -737,6 +737,10 @@ class XRound:
         self.np2, self.nl2 = np2, nl2
         self.ks1 = self.ks2 = 0  # Karatsuba products per job (set by check_xround)
         self.ef = 0  # the first product's operands are plain elements (compile_round)
+        # the linear-term job's REDC result is below (qmax + 1) p (check_xround);
+        # one_chain: reduced by bn256_redq.h's one-chain tail, which takes qmax as
+        # a template argument (ONE_CHAIN_PROGRAMS); lz: result left in [0, 2p)
+        self.qmax, self.one_chain, self.lz = 0, False, 0
 
         def negk(terms):
             return sum(-k for _, k in terms if k < 0)
@@ -795,10 +799,12 @@ class XRound:
         return b
 
 
-def compile_round(lanes, name, scratch_cap, lanes2=None, pre_lanes=16, ks_min=None):
+def compile_round(lanes, name, scratch_cap, lanes2=None, pre_lanes=16, ks_min=None, one_chain=False, lazy=False):
     """pre_lanes: lanes that evaluate the pre-pass values (16, or 12 for
     programs that also run in 12-lane teams: PRE_LANES); ks_min: the program's
-    Karatsuba threshold (KARATSUBA_MIN_PROG, default KARATSUBA_MIN)."""
+    Karatsuba threshold (KARATSUBA_MIN_PROG, default KARATSUBA_MIN);
+    one_chain: the program's linear-term rounds use the one-chain reduction
+    (ONE_CHAIN_PROGRAMS); lazy: they leave their result in [0, 2p)."""
     one_lc = [(REG["ONE"], 1)]
     values = {}      # canonical lincomb -> scratch code
     order = []
@@ -879,6 +885,8 @@ def compile_round(lanes, name, scratch_cap, lanes2=None, pre_lanes=16, ks_min=No
         out.append(L)
     xr = XRound(nv, nt, np_, nl, out, name, np2, nl2)
     xr.ef = ef
+    xr.one_chain = bool(one_chain and nl > 0)
+    xr.lz = int(lazy and nl > 0)
     try:
         check_xround(xr, order, ks_min)
     except AssertionError:
@@ -923,6 +931,8 @@ def check_xround(xr, order, ks_min=None):
             for u, v in prods for lb in (src_bound(u)[1], src_bound(v)[1]))
     xr.ks1 = int(all(ks_ok(L["prod"]) for L in xr.lanes))
     xr.ks2 = int(xr.fused and all(ks_ok(L["prod2"]) for L in xr.lanes))
+    qmax1 = 0
+    assert not (xr.one_chain and xr.fused), f"{xr.name}: a one-chain round is not fused"
     for prod, lin, kl, nl in jobs:
         L = {"prod": prod, "lin": lin}
         if kl < 0:
@@ -953,12 +963,47 @@ def check_xround(xr, order, ks_min=None):
         # exact range of fp_reduce8 (q <= 30 keeps q * p_l inside int32).
         if nl > 0:
             assert T / (1 << R_BITS) + P < 30 * P, f"{xr.name}: REDC result {T / (1 << R_BITS) / P:.1f} p"
+            # this job's own bound: V < T/R + p <= (q + 1) p
+            q = ((T >> R_BITS) + 1 + P) // P
+            qmax1 = max(qmax1, q)
+            if xr.one_chain:
+                check_one_chain(xr.name, q, max(cols[R_BITS // 26:]) + 11 * (1 << 52))
         else:
             assert T < P * (1 << R_BITS), f"{xr.name}: REDC input {T / P / P:.1f} p^2"
+    xr.qmax = qmax1
 
 
-def run_xround(xr, F, A, B):
-    """Interprets a compiled round on plain residues; returns {dst: value}."""
+# The one-chain reduction tail (bn256_redq.h redq_tail<QMAX, LAZY>): the
+# quotient estimate q = floor(t / (p9 + 1)), t = c9 + floor(c8 / 2^26), is taken
+# from the top two columns before they are normalised, and q (Z - p) is added
+# limb by limb in the normalising chain (Z: zero re-spread, REDQ_Z).
+ONE_CHAIN_PROGRAMS = ("LINE_FIX_12", "CYC_SQR_X_12")
+ONE_CHAIN_QMAX_LIMIT = 64   # kRedqMaxQ
+ONE_CHAIN_COMPARE_Q = 2     # kRedqCompareQ: up to here q is a sum of compares
+REDQ_Z = [1 << 26] + [(1 << 26) - 1] * 8
+assert sum(z << (26 * j) for j, z in enumerate(REDQ_Z)) == 1 << 234
+P_LIMBS = [(P >> (26 * j)) & ((1 << 26) - 1) for j in range(9)] + [P >> 234]
+
+
+def check_one_chain(name, qmax, cmax):
+    """Fails the build unless redq_tail<qmax> is exact for a job whose REDC
+    result is below (qmax + 1) p and whose columns 11..20 stay below cmax after
+    the REDC digits (bn256_redq.h has the derivation)."""
+    assert 1 <= qmax <= ONE_CHAIN_QMAX_LIMIT, f"{name}: quotient bound {qmax}"
+    d = P_LIMB_TOP + 1
+    # the chain's 64-bit sums: column + q (Z_j - p_j) + carry
+    assert cmax + qmax * (1 << 26) + (1 << 39) < 1 << 64, f"{name}: one-chain column overflow"
+    # the top limb and t in 32-bit arithmetic
+    assert (qmax + 2) * d + (1 << 14) < 1 << 32, f"{name}: one-chain top limb"
+    # 0 <= V - q p < (p9 + 1 + D + q) 2^234 with D = ceil(2 cmax / 2^52): below 2p
+    D = (2 * cmax + (1 << 52) - 1) >> 52
+    assert (P_LIMB_TOP + 1 + D + qmax) << 234 < 2 * P, f"{name}: one-chain result not below 2p"
+
+
+def run_xround(xr, F, A, B, limbs=False):
+    """Interprets a compiled round on plain residues; returns {dst: value}.
+    limbs: F, A, B hold limb vectors of Montgomery representatives and the
+    round runs limb for limb (xround_limbs), reduction tail included."""
     S = {}
 
     def get(code):
@@ -970,6 +1015,8 @@ def run_xround(xr, F, A, B):
             return A[code - SLOT_A]
         return F[code]
 
+    if limbs:
+        return xround_limbs(xr, get)[1]
     for L in xr.lanes:
         for dst, terms in L["pre"]:
             if dst != NONE:
@@ -1048,18 +1095,20 @@ def compile_all():
             X[name] = _compile_fused(name, ctx)
         else:
             X[name] = [compile_round(r, f"{name}[{i}]", SCRATCH_CAP[ctx], pre_lanes=PRE_LANES.get(name, 16),
-                                     ks_min=KARATSUBA_MIN_PROG.get(name))
+                                     ks_min=KARATSUBA_MIN_PROG.get(name), one_chain=name in ONE_CHAIN_PROGRAMS,
+                                     lazy=name in LAZY_PROGRAMS)
                        for i, r in enumerate(PROGRAMS[name])]
     return X
 
 
-def run_xprogram(rounds, F, A=None, B=None):
-    """F: register dict (mutated), A/B: slot element lists; returns the D slot (dict e -> v)."""
-    A = A or [0] * 12
-    B = B or [0] * 12
+def run_xprogram(rounds, F, A=None, B=None, limbs=False):
+    """F: register dict (mutated), A/B: slot element lists; returns the D slot (dict e -> v).
+    limbs: see run_xround."""
+    A = A or [to_limbs(0) if limbs else 0] * 12
+    B = B or [to_limbs(0) if limbs else 0] * 12
     D = {}
     for xr in rounds:
-        out = run_xround(xr, F, A, B)
+        out = run_xround(xr, F, A, B, limbs)
         for dst, v in out.items():
             if dst < 128:
                 F[dst] = v
@@ -1379,6 +1428,7 @@ def bind(xr, binding, ctx, layout=""):
     out.kp, out.kl1, out.kl2 = xr.kp, xr.kl1, xr.kl2
     out.ks1, out.ks2 = xr.ks1, xr.ks2
     out.ef = xr.ef
+    out.qmax, out.one_chain, out.lz = xr.qmax, xr.one_chain, xr.lz
     return out
 
 
@@ -1399,6 +1449,156 @@ def run_bound(rounds, mem):
             mem[d] = v
 
 
+# ------------------------------------------------------------------ limb-level interpreter
+# The executor's arithmetic word for word (bn256_xprog.h x_round, bn256_fp.h,
+# bn256_redq.h): elements are Montgomery representatives (x R mod p, or that
+# plus p for a lazy element) held as ten limbs, pre-pass values are 32-bit limb
+# sums, a job is 21 64-bit columns, REDC runs digit by digit, and the tail is
+# the round's own form. Every intermediate is asserted to fit its register.
+R_MONT = 1 << R_BITS
+P_INV26 = (-pow(P, -1, 1 << 26)) % (1 << 26)
+MASK26 = (1 << 26) - 1
+REDQ_D = P_LIMB_TOP + 1
+REDQ_M = (1 << 53) // REDQ_D + 1
+
+
+def to_limbs(v):
+    """An integer below 2^266 as ten limbs (nine of 26 bits, the top one whole)."""
+    return [(v >> (26 * j)) & MASK26 for j in range(9)] + [v >> 234]
+
+
+def from_limbs(l):
+    return sum(x << (26 * j) for j, x in enumerate(l))
+
+
+def redq_tail_model(c, qmax, lazy):
+    """redq_tail<qmax, lazy> on the columns 11..20 (ten 64-bit values)."""
+    assert 1 <= qmax <= ONE_CHAIN_QMAX_LIMIT and all(0 <= x < 1 << 64 for x in c)
+    t = ((c[9] & 0xFFFFFFFF) + ((c[8] >> 26) & 0xFFFFFFFF)) & 0xFFFFFFFF
+    if qmax <= ONE_CHAIN_COMPARE_Q:
+        q = sum(1 for k in range(1, qmax + 1) if t >= k * REDQ_D)
+    else:
+        assert t * REDQ_M < 1 << 64
+        q = (t * REDQ_M) >> 53
+    r, carry = [], 0
+    for j in range(9):
+        v = c[j] + q * (REDQ_Z[j] - P_LIMBS[j]) + carry
+        assert v < 1 << 64, "one-chain column overflow"
+        r.append(v & MASK26)
+        carry = v >> 26
+    r.append((((c[9] + carry) & 0xFFFFFFFF) - q * REDQ_D) & 0xFFFFFFFF)
+    if not lazy and r[9] >= P_LIMBS[9]:
+        s, br = [], 0
+        for i in range(10):
+            v = r[i] - P_LIMBS[i] - br
+            br = 1 if v < 0 else 0
+            s.append(v & MASK26)
+        if br == 0:
+            r = s
+    return r
+
+
+def reduce_wide_model(c, lazy):
+    """acc_reduce_wide / acc_reduce_wide_lazy's tail (bn256_team.h) on columns 11..20."""
+    x, carry = [], 0
+    for j in range(10):
+        v = (c[j] + carry) & ((1 << 64) - 1)
+        x.append(v & MASK26 if j < 9 else v & 0xFFFFFFFF)
+        carry = v >> 26
+    q = x[9] // REDQ_D
+    assert q <= 30
+    y, cy = [], 0
+    for i in range(10):
+        v = x[i] - q * P_LIMBS[i] + cy
+        assert -(1 << 31) <= v < 1 << 31
+        y.append(v & MASK26 if i < 9 else v & 0xFFFFFFFF)
+        cy = v >> 26
+    return y if lazy else _csub_model(y, rare=False)
+
+
+def _csub_model(x, rare):
+    if rare and x[9] < P_LIMBS[9]:
+        return list(x)
+    s, br = [], 0
+    for i in range(10):
+        v = x[i] - P_LIMBS[i] - br
+        br = 1 if v < 0 else 0
+        s.append(v & MASK26)
+    return list(x) if br else s
+
+
+def _lincomb_model(terms, k, read):
+    """x_lincomb_sum: 32-bit limb sums with the correction K (4p)''."""
+    if k < 0:
+        k = sum(-c for _, c in terms if c < 0)
+    out = [k * z for z in P2N]
+    for src, c in terms:
+        x = read(src)
+        out = [a + c * b for a, b in zip(out, x)]
+    assert all(0 <= v < 1 << 32 for v in out), "limb sum outside 32 bits"
+    return out
+
+
+def xround_limbs(xr, read):
+    """One round on limb vectors. read(code) -> the ten limbs of an operand
+    that the pre-pass does not write. Returns (pre, out): the pre-pass values
+    and the jobs' results, both {destination: limbs}."""
+    pre = {}
+    for L in xr.lanes:
+        for dst, terms in L["pre"]:
+            if dst != NONE:
+                pre[dst] = _lincomb_model(terms, xr.kp, read)
+
+    def rd(code):
+        return pre[code] if code in pre else read(code)
+
+    out = {}
+    for L in xr.lanes:
+        for pk, lk, dk, kl, second in (("prod", "lin", "dst", xr.kl1, False), ("prod2", "lin2", "dst2", xr.kl2, True)):
+            if dk not in L or L[dk] == NONE:
+                continue
+            nl = xr.nl2 if second else xr.nl
+            cols = [0] * 21
+            if nl > 0:
+                cols[11:21] = _lincomb_model(L[lk], kl, rd)
+            for u, v in L[pk]:
+                a, b = rd(u), rd(v)
+                for i in range(10):
+                    for j in range(10):
+                        cols[i + j] += a[i] * b[j]
+            for i in range(11):  # acc_redc_digit
+                q = (cols[i] * P_INV26) & MASK26
+                for j in range(10):
+                    cols[i + j] += q * P_LIMBS[j]
+                cols[i + 1] += cols[i] >> 26
+            assert all(c < 1 << 64 for c in cols), "column overflow"
+            if nl > 0 and xr.one_chain and not second:
+                r = redq_tail_model(cols[11:], xr.qmax, bool(xr.lz))
+            elif nl > 0:
+                r = reduce_wide_model(cols[11:], bool(xr.lz) and not second)
+            else:  # acc_reduce: acc_redc_limbs and fp_csub_rare
+                x, carry = [], 0
+                for j in range(10):
+                    v = cols[11 + j] + carry
+                    x.append(v & MASK26 if j < 9 else v & 0xFFFFFFFF)
+                    carry = v >> 26
+                r = _csub_model(x, rare=True)
+            val = from_limbs(r)
+            assert all(x <= MASK26 for x in r[:9]) and val < (2 * P if xr.lz else P), f"{xr.name}: result range"
+            assert L[dk] not in out, "two jobs write one destination"
+            out[L[dk]] = r
+    return pre, out
+
+
+def run_bound_limbs(rounds, mem):
+    """run_bound limb for limb: mem holds limb vectors of Montgomery
+    representatives (to_limbs(x R mod p), lazy ones plus p)."""
+    for xr in rounds:
+        pre, out = xround_limbs(xr, lambda code: mem[code])
+        for d, v in list(pre.items()) + list(out.items()):
+            mem[d] = v
+
+
 def check_instances(X, seed=3):
     """Every bound instance computes the same as the abstract program."""
     rng = random.Random(seed)
@@ -1416,7 +1616,12 @@ def check_instances(X, seed=3):
             A = mem[12 * SLOTS.index(bd[1]):12 * SLOTS.index(bd[1]) + 12]
             B = mem[12 * SLOTS.index(bd[2]):12 * SLOTS.index(bd[2]) + 12]
         want_D = run_xprogram(X[name], F, A, B)
+        # the limb-level model of the same instance (Montgomery representatives)
+        lmem = [to_limbs(v * R_MONT % P) for v in mem]
         run_bound(rounds, mem)
+        run_bound_limbs(rounds, lmem)
+        rinv = pow(R_MONT, -1, P)
+        assert all(from_limbs(l) * rinv % P == v for l, v in zip(lmem, mem)), f"instance {name}{binding}: limb model"
         if binding:
             d0 = 12 * SLOTS.index(binding[0])
             assert all(mem[d0 + e] == v for e, v in want_D.items()), f"instance {name}{binding}"
@@ -1516,8 +1721,11 @@ def emit_x(X, path):
             nxt = f"XHint{{{rounds[i + 1][1]}, {rounds[i + 1][0].words()}}}" if i + 1 < len(rounds) else "h"
             lz = int(name in LAZY_PROGRAMS and bx.nl > 0)
             assert not (lz and bx.fused), "a lazy round is not fused"
+            assert lz == bx.lz, f"{name}: lazy flag"
             fu = int(REDC_FUSE[name] and not bx.fused)  # a two-job round never fuses
-            calls.append(f"x_round<{bx.nv}, {bx.nt}, {bx.np}, {bx.nl}, {bx.words()}, {bx.np2}, {bx.nl2}, "
+            # one-chain rounds carry their quotient bound: XQ<QMAX>::x_round<...>
+            xq = f"XQ<{bx.qmax}>::" if bx.one_chain else ""
+            calls.append(f"{xq}x_round<{bx.nv}, {bx.nt}, {bx.np}, {bx.nl}, {bx.words()}, {bx.np2}, {bx.nl2}, "
                          f"{bx.kp}, {bx.kl1}, {bx.kl2}, {bx.ks1}, {bx.ks2}, {lz}, {bx.ef}, {fu}>(T, S, {off}, {nxt});")
         args = ", ".join(f"S_{b}" for b in binding)
         targs = f"XP_{name}{'_' + layout if layout else ''}" + (", " + args if args else "")
