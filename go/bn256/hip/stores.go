@@ -16,7 +16,9 @@ import (
 // host store stays authoritative: Store / unsafeCheckMerge (store.go:82-226)
 // run on the host once per verified signature and the changed levels are
 // pushed with Update; only Evaluate (store.go:101-183), which runs once per
-// queued signature per step, runs on the device.
+// queued signature per step, runs on the device. That is the default; after
+// EnableMerge the signatures are resident too and MergeDevice / Combined run
+// the rest of the store on the device (see below).
 //
 // A Stores belongs to the registry its engine held when it was made: after a
 // later LoadRegistry every call fails. Close it before its engine.
@@ -155,6 +157,147 @@ func (s *Stores) SelectDevice(dPkts unsafe.Pointer, n int, dScores unsafe.Pointe
 	rc := C.hg_stores_select_device(s.h, (*C.hg_packet)(dPkts), C.size_t(n), (*C.int32_t)(dScores), C.uint32_t(k),
 		(*C.hg_request)(dReqs), (*C.uint8_t)(dSigs), (*C.uint32_t)(dSel), (*C.uint32_t)(dCount),
 		(*C.hg_request)(dOutReqs), (*C.uint8_t)(dOutSigs), stream)
+	if rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}
+
+// StoreSig is one signature loaded into a merge-enabled Stores: Level 0 is the
+// receiver's own signature (Index ignored); Index = BestSig loads the level's
+// best signature, any other Index the individual signature at that mapped
+// index of the level. Sig is the 64-byte marshal.
+type StoreSig struct {
+	Receiver, Level int
+	Index           uint32
+	Sig             []byte
+}
+
+// BestSig is StoreSig.Index for a level's best signature; FullLevel is
+// StoreQuery.Level for FullSignature.
+const (
+	BestSig   = uint32(C.HG_STORE_SIG_BEST)
+	FullLevel = uint32(C.HG_STORE_LEVEL_FULL)
+)
+
+// StoreQuery names one Combined(level) (store.go:248-262), or, with Level =
+// FullLevel, one FullSignature (store.go:238-246).
+type StoreQuery struct {
+	Receiver int
+	Level    uint32
+}
+
+// Combined is one outgoing multisignature: Code is HG_OK, HG_COMBINED_EMPTY
+// (the reference returns nil), HG_COMBINED_ERR_MISSING or HG_ERR_ARG.
+type Combined struct {
+	Code      int32
+	BitLength int
+	Words     []uint64
+	Sig       []byte
+}
+
+// EnableMerge makes the store complete on the device: the best signatures, the
+// own signature and the verified individual signatures become resident, and
+// MergeDevice / Combined replace the host store's Store / unsafeCheckMerge
+// (store.go:82-229) and Combined / FullSignature. Opt-in: a Stores that never
+// calls it behaves as before.
+func (s *Stores) EnableMerge() error {
+	if rc := C.hg_stores_enable_merge(s.h); rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}
+
+// UpdateSigs loads signatures from the host (seeding, and a host store's
+// mirror), each target named at most once. Call it after Update: Update clears
+// a level's "best signature known" bit.
+func (s *Stores) UpdateSigs(sigs []StoreSig) error {
+	if len(sigs) == 0 {
+		return nil
+	}
+	recs := make([]C.hg_store_sig, len(sigs))
+	buf := make([]byte, 0, 64*len(sigs))
+	for i, g := range sigs {
+		if len(g.Sig) != 64 {
+			return &DeviceError{Code: C.HG_ERR_ARG, Msg: "UpdateSigs: a signature marshal is 64 bytes"}
+		}
+		recs[i] = C.hg_store_sig{receiver: C.uint32_t(g.Receiver), level: C.uint32_t(g.Level),
+			index: C.uint32_t(g.Index), sig_off: C.uint32_t(i)}
+		buf = append(buf, g.Sig...)
+	}
+	rc := C.hg_stores_update_sigs(s.h, &recs[0], C.size_t(len(recs)), bytePtr(buf), C.size_t(len(sigs)))
+	if rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}
+
+// ReadBest returns one level's best (store.go:231-236 Best): its bitset's
+// words, its signature, whether there is one and whether its signature is
+// held. Level 0 is the own signature.
+func (s *Stores) ReadBest(receiver, level int) (best []uint64, sig []byte, hasBest, sigKnown bool, err error) {
+	best = make([]uint64, s.stride)
+	sig = make([]byte, 64)
+	var flags C.int
+	rc := C.hg_stores_read_best(s.h, C.uint32_t(receiver), C.uint32_t(level), wordPtr(best), bytePtr(sig), &flags)
+	if rc != C.HG_OK {
+		return nil, nil, false, false, s.e.fail(rc)
+	}
+	return best, sig, flags&C.HG_STORE_HAS_BEST != 0, flags&C.HG_STORE_BEST_SIG != 0, nil
+}
+
+// MergeDevice is store.go:82-99 Store for the picks of one intake step, on
+// device arrays and asynchronous on stream: dSel / dCount are SelectDevice's
+// output, dVcodes the verdicts of hg_verify_aggregate_device over the same
+// capacity, dPkts / dWords / dSigs the parse outputs. dResults receives one
+// HG_MERGE_* per entry, dChanged / dNChanged the (receiver, level) pairs whose
+// best changed.
+func (s *Stores) MergeDevice(dPkts unsafe.Pointer, n int, dSel, dCount unsafe.Pointer, capacity int,
+	dVcodes unsafe.Pointer, stride int, dWords, dSigs, dResults, dChanged, dNChanged, stream unsafe.Pointer) error {
+	rc := C.hg_stores_merge_device(s.h, (*C.hg_packet)(dPkts), C.size_t(n), (*C.uint32_t)(dSel),
+		(*C.uint32_t)(dCount), C.size_t(capacity), (*C.int32_t)(dVcodes), C.size_t(stride), (*C.uint64_t)(dWords),
+		(*C.uint8_t)(dSigs), (*C.int32_t)(dResults), (*C.uint32_t)(dChanged), (*C.uint32_t)(dNChanged), stream)
+	if rc != C.HG_OK {
+		return s.e.fail(rc)
+	}
+	return nil
+}
+
+// Combined answers the queries with the multisignatures Handel sends: the
+// bests of levels <= Level in the range the peers of Level+1 expect, or the
+// full signature. wordsStride words per result (at least ceil(N/64) when a
+// full query is among them).
+func (s *Stores) Combined(queries []StoreQuery, wordsStride int) ([]Combined, error) {
+	m := len(queries)
+	if m == 0 {
+		return nil, nil
+	}
+	qs := make([]C.hg_store_query, m)
+	for i, q := range queries {
+		qs[i] = C.hg_store_query{receiver: C.uint32_t(q.Receiver), level: C.uint32_t(q.Level)}
+	}
+	codes := failedCodes(m)
+	bitlens := make([]uint32, m)
+	words := make([]uint64, m*wordsStride)
+	sigs := make([]byte, 64*m)
+	rc := C.hg_stores_combined(s.h, &qs[0], C.size_t(m), C.size_t(wordsStride), codePtr(codes),
+		(*C.uint32_t)(unsafe.Pointer(&bitlens[0])), wordPtr(words), bytePtr(sigs))
+	if rc != C.HG_OK {
+		return nil, s.e.fail(rc)
+	}
+	out := make([]Combined, m)
+	for i := range out {
+		out[i] = Combined{Code: codes[i], BitLength: int(bitlens[i]),
+			Words: words[i*wordsStride : (i+1)*wordsStride], Sig: sigs[64*i : 64*i+64]}
+	}
+	return out, nil
+}
+
+// CombinedDevice is Combined on device arrays, asynchronous on stream.
+func (s *Stores) CombinedDevice(dQueries unsafe.Pointer, m, wordsStride int, dCodes, dBitlens, dWords, dSigs,
+	stream unsafe.Pointer) error {
+	rc := C.hg_stores_combined_device(s.h, (*C.hg_store_query)(dQueries), C.size_t(m), C.size_t(wordsStride),
+		(*C.int32_t)(dCodes), (*C.uint32_t)(dBitlens), (*C.uint64_t)(dWords), (*C.uint8_t)(dSigs), stream)
 	if rc != C.HG_OK {
 		return s.e.fail(rc)
 	}

@@ -42,6 +42,17 @@ HG_ERR_PKT_ID_RANGE = 28
 HG_PKT_NO_IND = 29
 HG_PKT_HAS_IND = 1
 HG_STORE_HAS_BEST = 1
+HG_STORE_BEST_SIG = 2
+HG_STORE_SIG_BEST = 0xFFFFFFFF
+HG_STORE_LEVEL_FULL = 0xFFFFFFFF
+HG_MERGE_SKIPPED = 0
+HG_MERGE_STORED = 1
+HG_MERGE_DISCARDED = 2
+HG_MERGE_ERR_MISSING = 3
+HG_MERGE_ERR_INDIVIDUAL = 4
+HG_MERGE_ERR_ROW = 5
+HG_COMBINED_EMPTY = 1
+HG_COMBINED_ERR_MISSING = 2
 HG_ERR_ARG = 100
 HG_ERR_DEVICE = 101
 
@@ -113,6 +124,12 @@ SIGNATURES = {
     "hg_stores_evaluate": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P]),
     "hg_stores_select_capacity": (_SZ, [_P, _SZ, ctypes.c_uint32]),
     "hg_stores_select_device": (_I, [_P, _P, _SZ, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_stores_enable_merge": (_I, [_P]),
+    "hg_stores_update_sigs": (_I, [_P, _P, _SZ, _P, _SZ]),
+    "hg_stores_read_best": (_I, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, ctypes.POINTER(_I)]),
+    "hg_stores_merge_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
+    "hg_stores_combined_device": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    "hg_stores_combined": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P]),
     "hg_batcher_create": (_I, [_P, _SZ, ctypes.c_uint, ctypes.POINTER(_P)]),
     "hg_batcher_destroy": (None, [_P]),
     "hg_batcher_submit": (_I, [_P, _P, _SZ, _P, _P, _P, ctypes.POINTER(_P)]),

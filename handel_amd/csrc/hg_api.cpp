@@ -341,9 +341,23 @@ struct hg_stores {
   DevBuf<uint64_t> keys_a, keys_b;
   DevBuf<uint32_t> cnt, picks, base;
   DevBuf<uint8_t> temp;
+  // merge (hg_stores_enable_merge; hg_merge.hip): the signature tables, the
+  // merge's per-entry workspaces and the staging of the host-pointer calls
+  bool merge = false;
+  DevBuf<uint8_t> best_sig, indiv_sig;
+  DevBuf<uint64_t> held;
+  DevBuf<uint32_t> own, m_rows, m_marks;
+  DevBuf<hg_store_sig> sig_recs;
+  DevBuf<uint8_t> sig_bytes;
+  DevBuf<hg_store_query> q_in;
+  DevBuf<int32_t> q_codes;
+  DevBuf<uint32_t> q_bitlens;
+  DevBuf<uint64_t> q_words;
+  DevBuf<uint8_t> q_sigs;
   StoreTab table() const {
     return StoreTab{tab.p, flags.p, d_map.p, (uint32_t)nreg, levels, stride, (int)receivers.size()};
   }
+  StoreMergeTab merge_table() const { return StoreMergeTab{best_sig.p, indiv_sig.p, held.p, own.p}; }
   void release() {
     tab.release();
     flags.release();
@@ -361,6 +375,20 @@ struct hg_stores {
     picks.release();
     base.release();
     temp.release();
+    best_sig.release();
+    indiv_sig.release();
+    held.release();
+    own.release();
+    m_rows.release();
+    m_marks.release();
+    sig_recs.release();
+    sig_bytes.release();
+    q_in.release();
+    q_codes.release();
+    q_bitlens.release();
+    q_words.release();
+    q_sigs.release();
+    merge = false;
   }
 };
 
@@ -1974,6 +2002,183 @@ int hg_stores_select_device(hg_stores* st, const hg_packet* d_pkts, size_t n, co
                                     d_out_reqs, d_out_sigs, (uint32_t)cap, s));
   }
   HG_CHECK(c, sub.finish());
+  return HG_OK;
+}
+
+// ---------------------------------------------------------------- stores: merge and Combined
+int hg_stores_enable_merge(hg_stores* st) {
+  if (!st) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st)) return HG_ERR_ARG;
+  if (st->merge) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  const size_t S = st->receivers.size();
+  const size_t rows = S * (size_t)st->levels;
+  HG_CHECK(c, st->best_sig.ensure(rows * 64));
+  HG_CHECK(c, st->indiv_sig.ensure(S * st->nreg * 64));
+  HG_CHECK(c, st->held.ensure(rows * st->stride));
+  HG_CHECK(c, st->own.ensure(S));
+  HG_CHECK(c, st->m_rows.ensure(2 * st->max_packets));
+  HG_CHECK(c, st->m_marks.ensure(2 * st->max_packets));
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemsetAsync(st->best_sig.p, 0, st->best_sig.cap, c->stream));
+  HG_CHECK(c, hipMemsetAsync(st->indiv_sig.p, 0, st->indiv_sig.cap, c->stream));
+  HG_CHECK(c, hipMemsetAsync(st->held.p, 0, st->held.cap * sizeof(uint64_t), c->stream));
+  HG_CHECK(c, hipMemsetAsync(st->own.p, 0, st->own.cap * sizeof(uint32_t), c->stream));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  st->merge = true;
+  return HG_OK;
+}
+
+int hg_stores_update_sigs(hg_stores* st, const hg_store_sig* recs, size_t n, const uint8_t* sigs, size_t n_sigs) {
+  if (!st || (n && (!recs || !sigs))) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !st->merge) return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  if (n > (size_t)INT32_MAX) return HG_ERR_ARG;
+  for (size_t i = 0; i < n; i++) {
+    const hg_store_sig& r = recs[i];
+    if (r.receiver >= st->nreg || st->map[r.receiver] < 0 || r.sig_off >= n_sigs) return HG_ERR_ARG;
+    if (r.level == 0) continue;
+    uint32_t lo = 0, hi = 0;
+    if (r.level > (uint32_t)st->levels || !pkt_range_level(r.receiver, (uint32_t)st->nreg, (int)r.level, lo, hi))
+      return HG_ERR_ARG;
+    if (r.index != HG_STORE_SIG_BEST && r.index >= hi - lo) return HG_ERR_ARG;
+  }
+  HG_CHECK(c, hipSetDevice(c->device));
+  HG_CHECK(c, st->sig_recs.ensure(n));
+  HG_CHECK(c, st->sig_bytes.ensure(n_sigs * 64));
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(st->sig_recs.p, recs, n * sizeof(hg_store_sig), hipMemcpyHostToDevice, c->stream));
+  HG_CHECK(c, hipMemcpyAsync(st->sig_bytes.p, sigs, n_sigs * 64, hipMemcpyHostToDevice, c->stream));
+  launch_store_update_sigs(st->table(), st->merge_table(), st->sig_recs.p, (int)n, st->sig_bytes.p, c->stream);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+
+int hg_stores_read_best(hg_stores* st, uint32_t receiver, uint32_t level, uint64_t* best, uint8_t* sig, int* flags) {
+  if (!st) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !st->merge) return HG_ERR_ARG;
+  if (receiver >= st->nreg || st->map[receiver] < 0 || level > (uint32_t)st->levels) return HG_ERR_ARG;
+  HG_CHECK(c, hipSetDevice(c->device));
+  const size_t s = (size_t)st->map[receiver];
+  uint32_t fl = 0;
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  if (level == 0) {
+    if (sig)
+      HG_CHECK(c, hipMemcpyAsync(sig, st->indiv_sig.p + (s * st->nreg + receiver) * 64, 64, hipMemcpyDeviceToHost,
+                                 c->stream));
+    HG_CHECK(c, hipMemcpyAsync(&fl, st->own.p + s, sizeof(fl), hipMemcpyDeviceToHost, c->stream));
+  } else {
+    const size_t row = s * st->levels + (level - 1);
+    if (best)
+      HG_CHECK(c, hipMemcpyAsync(best, st->tab.p + 2 * row * st->stride, (size_t)st->stride * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, c->stream));
+    if (sig) HG_CHECK(c, hipMemcpyAsync(sig, st->best_sig.p + row * 64, 64, hipMemcpyDeviceToHost, c->stream));
+    HG_CHECK(c, hipMemcpyAsync(&fl, st->flags.p + row, sizeof(fl), hipMemcpyDeviceToHost, c->stream));
+  }
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  if (level == 0) {
+    fl = (fl & 1u) ? (HG_STORE_HAS_BEST | HG_STORE_BEST_SIG) : 0u;
+    if (best) {
+      for (int w = 0; w < st->stride; w++) best[w] = 0;
+      best[0] = fl ? 1u : 0u;
+    }
+  }
+  if (flags) *flags = (int)(fl & (HG_STORE_HAS_BEST | HG_STORE_BEST_SIG));
+  return HG_OK;
+}
+
+int hg_stores_merge_device(hg_stores* st, const hg_packet* d_pkts, size_t n, const uint32_t* d_sel,
+                           const uint32_t* d_count, size_t capacity, const int32_t* d_vcodes, size_t stride_words,
+                           const uint64_t* d_words, const uint8_t* d_sigs, int32_t* d_results, uint32_t* d_changed,
+                           uint32_t* d_nchanged, void* stream) {
+  if (!st || !d_nchanged ||
+      (capacity && (!d_pkts || !d_sel || !d_vcodes || !d_words || !d_sigs || !d_results || !d_changed)))
+    return HG_ERR_ARG;
+  if ((uintptr_t)d_sigs & 3) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !st->merge || !stores_slots_ok(st, n, stride_words) || n > st->max_packets ||
+      capacity > 2 * st->max_packets)
+    return HG_ERR_ARG;
+  HG_CHECK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  const StoreMergeWs ws{st->m_rows.p, st->m_marks.p};
+  launch_store_merge(st->table(), st->merge_table(), ws, d_pkts, (int)n, d_sel, d_count, (uint32_t)capacity, d_vcodes,
+                     (int)stride_words, d_words, d_sigs, d_results, d_changed, d_nchanged, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  return HG_OK;
+}
+
+int hg_stores_combined_device(hg_stores* st, const hg_store_query* d_queries, size_t m, size_t words_stride,
+                              int32_t* d_codes, uint32_t* d_bitlens, uint64_t* d_words, uint8_t* d_sigs,
+                              void* stream) {
+  if (!st || (m && (!d_queries || !d_codes || !d_bitlens || !d_words || !d_sigs))) return HG_ERR_ARG;
+  if ((uintptr_t)d_sigs & 3) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !st->merge || m > (size_t)INT32_MAX || words_stride == 0 ||
+      words_stride > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (m == 0) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  launch_store_combined(st->table(), st->merge_table(), d_queries, (int)m, (int)words_stride, d_codes, d_bitlens,
+                        d_words, d_sigs, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  return HG_OK;
+}
+
+int hg_stores_combined(hg_stores* st, const hg_store_query* queries, size_t m, size_t words_stride, int32_t* codes,
+                       uint32_t* bitlens, uint64_t* words, uint8_t* sigs) {
+  if (!st || (m && (!queries || !codes || !bitlens || !words || !sigs))) return HG_ERR_ARG;
+  hg_ctx* c = st->c;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!stores_current(st) || !st->merge || m > (size_t)INT32_MAX || words_stride == 0 ||
+      words_stride > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (m == 0) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  HG_CHECK(c, st->q_in.ensure(m));
+  HG_CHECK(c, st->q_codes.ensure(m));
+  HG_CHECK(c, st->q_bitlens.ensure(m));
+  HG_CHECK(c, st->q_words.ensure(m * words_stride));
+  HG_CHECK(c, st->q_sigs.ensure(m * 64));
+  hipStream_t s = c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(st->q_in.p, queries, m * sizeof(hg_store_query), hipMemcpyHostToDevice, s));
+  launch_store_combined(st->table(), st->merge_table(), st->q_in.p, (int)m, (int)words_stride, st->q_codes.p,
+                        st->q_bitlens.p, st->q_words.p, st->q_sigs.p, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(codes, st->q_codes.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, hipMemcpyAsync(bitlens, st->q_bitlens.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, hipMemcpyAsync(words, st->q_words.p, m * words_stride * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, hipMemcpyAsync(sigs, st->q_sigs.p, m * 64, hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(s));
   return HG_OK;
 }
 

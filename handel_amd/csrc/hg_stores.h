@@ -54,4 +54,37 @@ hipError_t launch_store_select(const StoreTab& t, const StoreSelectWs& ws, const
                                uint32_t* sel, uint32_t* count, hg_request* out_reqs, uint8_t* out_sigs,
                                uint32_t capacity, hipStream_t s);
 
+// ---------------------------------------------------------------- merge (hg_merge.hip)
+// The signature tables of a merge-enabled hg_stores, beside StoreTab's rows:
+// best_sig[64 * r]: the 64-byte marshal of row r's best (StoreTab::flags[r]
+// bit 1 = known); held[r * stride ...]: the level's individual signatures that
+// are held; indiv_sig[64 * (s * nreg + id)]: the individual signature of
+// registry id `id` in store s, the store's own id holding the level-0 (own)
+// signature; own[s] bit 0 = held.
+struct StoreMergeTab {
+  uint8_t* best_sig;
+  uint8_t* indiv_sig;
+  uint64_t* held;
+  uint32_t* own;
+};
+
+// Workspaces of one merge over `capacity` entries (device pointers).
+struct StoreMergeWs {
+  uint32_t* rows;   // capacity: row of every applied entry, 0xffffffff otherwise
+  uint32_t* marks;  // capacity: 1 at the first entry of a row whose best changed
+};
+
+// hg_stores_update_sigs' scatter: 16 lanes per record
+void launch_store_update_sigs(const StoreTab& t, const StoreMergeTab& m, const hg_store_sig* recs, int n,
+                              const uint8_t* sigs, hipStream_t s);
+// hg_stores_merge_device: results[capacity], changed[2 * capacity], nchanged[1]
+void launch_store_merge(const StoreTab& t, const StoreMergeTab& m, const StoreMergeWs& ws, const hg_packet* pkts, int n,
+                        const uint32_t* sel, const uint32_t* count, uint32_t capacity, const int32_t* vcodes,
+                        int slot_stride, const uint64_t* words, const uint8_t* sigs, int32_t* results,
+                        uint32_t* changed, uint32_t* nchanged, hipStream_t s);
+// hg_stores_combined*: one wave per query
+void launch_store_combined(const StoreTab& t, const StoreMergeTab& m, const hg_store_query* queries, int nq,
+                           int out_stride, int32_t* codes, uint32_t* bitlens, uint64_t* words, uint8_t* sigs,
+                           hipStream_t s);
+
 }  // namespace hg

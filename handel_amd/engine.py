@@ -28,6 +28,9 @@ PACKET_DTYPE = np.dtype([("origin", "<i4"), ("receiver", "<u4"), ("level", "<u4"
 # hg_store_update (include/handel_gpu.h): one (receiver, level) state pushed to the device stores
 STORE_UPDATE_DTYPE = np.dtype([("receiver", "<u4"), ("level", "<u4"), ("flags", "<u4"), ("best_off", "<u4"),
                                ("indiv_off", "<u4")])
+# hg_store_sig / hg_store_query (include/handel_gpu.h): a signature loaded into, a Combined query of, merge-enabled stores
+STORE_SIG_DTYPE = np.dtype([("receiver", "<u4"), ("level", "<u4"), ("index", "<u4"), ("sig_off", "<u4")])
+STORE_QUERY_DTYPE = np.dtype([("receiver", "<u4"), ("level", "<u4")])
 
 
 def _ptr(a) -> Optional[int]:
@@ -522,6 +525,68 @@ class Stores:
         self.engine._check(self.L.hg_stores_select_device(self.h, d_pkts, n, d_scores, int(k), d_reqs, d_sigs, d_sel,
                                                           d_count, d_out_reqs, d_out_sigs, stream or None),
                            "hg_stores_select_device")
+
+    # -- the opt-in device store: merge and Combined (hg_merge.hip)
+    def enable_merge(self) -> None:
+        """Allocates the signature tables (hg_stores_enable_merge): the set then
+        also runs store.go's Store / unsafeCheckMerge and Combined."""
+        self.engine._check(self.L.hg_stores_enable_merge(self.h), "hg_stores_enable_merge")
+
+    def update_sigs(self, recs: np.ndarray, sigs) -> None:
+        """Loads signatures from the host (hg_stores_update_sigs): recs of
+        STORE_SIG_DTYPE, sigs the 64-byte marshals recs' sig_off index."""
+        recs = np.ascontiguousarray(recs, dtype=STORE_SIG_DTYPE)
+        sigs = _u8(sigs)
+        if len(sigs) % 64:
+            raise ValueError("sigs must hold 64-byte marshals")
+        self.engine._check(self.L.hg_stores_update_sigs(self.h, _ptr(recs) if len(recs) else None, len(recs),
+                                                        _ptr(sigs) if len(sigs) else None, len(sigs) // 64),
+                           "hg_stores_update_sigs")
+
+    def read_best(self, receiver: int, level: int) -> Tuple[np.ndarray, bytes, int]:
+        """(best words, best signature, HG_STORE_HAS_BEST | HG_STORE_BEST_SIG
+        flags) of one level; level 0 is the own signature (hg_stores_read_best)."""
+        best = np.zeros(self.stride, dtype=np.uint64)
+        sig = np.zeros(64, dtype=np.uint8)
+        flags = ctypes.c_int()
+        self.engine._check(self.L.hg_stores_read_best(self.h, int(receiver), int(level), _ptr(best), _ptr(sig),
+                                                      ctypes.byref(flags)), "hg_stores_read_best")
+        return best, sig.tobytes(), int(flags.value)
+
+    def merge_device(self, d_pkts: int, n: int, d_sel: int, d_count: int, capacity: int, d_vcodes: int, stride: int,
+                     d_words: int, d_sigs: int, d_results: int, d_changed: int, d_nchanged: int,
+                     stream: int = 0) -> None:
+        """hg_stores_merge_device on raw device pointers (asynchronous):
+        store.go:82-99 Store for the verified picks of one intake step."""
+        self.engine._check(self.L.hg_stores_merge_device(self.h, d_pkts or None, n, d_sel or None, d_count or None,
+                                                         int(capacity), d_vcodes or None, int(stride),
+                                                         d_words or None, d_sigs or None, d_results or None,
+                                                         d_changed or None, d_nchanged or None, stream or None),
+                           "hg_stores_merge_device")
+
+    def combined_device(self, d_queries: int, m: int, words_stride: int, d_codes: int, d_bitlens: int, d_words: int,
+                        d_sigs: int, stream: int = 0) -> None:
+        """hg_stores_combined_device on raw device pointers (asynchronous)."""
+        self.engine._check(self.L.hg_stores_combined_device(self.h, d_queries or None, int(m), int(words_stride),
+                                                            d_codes or None, d_bitlens or None, d_words or None,
+                                                            d_sigs or None, stream or None),
+                           "hg_stores_combined_device")
+
+    def combined(self, queries, words_stride: Optional[int] = None):
+        """store.go:248-262 Combined / :238-246 FullSignature for (receiver,
+        level) queries (level HG_STORE_LEVEL_FULL: the full signature):
+        (codes, bit lengths, words[m, words_stride], signatures[m, 64])."""
+        q = np.ascontiguousarray(queries, dtype=STORE_QUERY_DTYPE)
+        m = len(q)
+        ws = (int(self.engine.L.hg_registry_size(self.engine.ctx)) + 63) // 64 if words_stride is None else int(words_stride)
+        codes = np.zeros(m, dtype=np.int32)
+        bitlens = np.zeros(m, dtype=np.uint32)
+        words = np.zeros((m, ws), dtype=np.uint64)
+        sigs = np.zeros((m, 64), dtype=np.uint8)
+        if m:
+            self.engine._check(self.L.hg_stores_combined(self.h, _ptr(q), m, ws, _ptr(codes), _ptr(bitlens),
+                                                         _ptr(words), _ptr(sigs)), "hg_stores_combined")
+        return codes, bitlens, words, sigs
 
 
 class DeviceLane:

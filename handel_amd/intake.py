@@ -4,10 +4,13 @@
 Handel scores every queued signature against its store and verifies only the
 best (processing.go:171-220 readTodos over store.go:101-183 Evaluate).
 `DeviceStores` keeps the scoring state of the hosted Handel instances on the
-device (hg_stores_*); the host `sigprocessing.Store` stays authoritative:
-`Store.store` / unsafeCheckMerge run on the host once per verified signature
-and `mirror` pushes the levels that changed. `DeviceIntake` is one intake step
-for a batch of raw packets of several instances.
+device (hg_stores_*); by default the host `sigprocessing.Store` stays
+authoritative: `Store.store` / unsafeCheckMerge run on the host once per
+verified signature and `mirror` pushes the levels that changed. `DeviceIntake`
+is one intake step for a batch of raw packets of several instances. With
+`DeviceIntake(device_merge=True)` the store is complete on the device
+(hg_stores_enable_merge): the step ends with hg_stores_merge_device on the
+same stream, and `best` / `combined` read the device's multisignatures.
 
 `select_reference` / `select_slots` restate the selection rule on plain
 integers (the picks and the order the rest goes back to the queue in); they
@@ -22,8 +25,9 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import partitioner as part
-from ._lib import HG_OK, HG_STORE_HAS_BEST, HandelGPUError
-from .engine import REQ_DTYPE, STORE_UPDATE_DTYPE, Engine, Stores
+from ._lib import (HG_COMBINED_EMPTY, HG_MERGE_DISCARDED, HG_MERGE_STORED, HG_OK, HG_STORE_BEST_SIG,
+                   HG_STORE_HAS_BEST, HG_STORE_LEVEL_FULL, HG_STORE_SIG_BEST, HandelGPUError)
+from .engine import REQ_DTYPE, STORE_SIG_DTYPE, STORE_UPDATE_DTYPE, Engine, Stores
 from .packets import Packet, pack_packets
 from .sigprocessing import IncomingSig, IndividualSigFilter, MultiSig, Store, bits_to_int, int_to_words
 
@@ -82,6 +86,12 @@ class DeviceStores(Stores):
     def __init__(self, engine: Engine, receivers: Sequence[int], max_packets: int, n_registry: Optional[int] = None):
         super().__init__(engine, receivers, max_packets)
         self.n = int(engine.L.hg_registry_size(engine.ctx)) if n_registry is None else int(n_registry)
+        self.merge_enabled = False
+        self._pushed: Dict[Tuple[int, int], set] = {}  # (receiver, level) -> individual signatures on the device
+
+    def enable_merge(self) -> None:
+        super().enable_merge()
+        self.merge_enabled = True
 
     def mirror(self, receiver: int, store: Store, levels: Optional[Iterable[int]] = None) -> None:
         """Pushes `store`'s state of `levels` (default: every level) to the
@@ -92,7 +102,16 @@ class DeviceStores(Stores):
     def mirror_many(self, items: Sequence[Tuple[int, Store, Optional[Iterable[int]]]]) -> None:
         """`mirror` for several stores in one hg_stores_update."""
         ups, words, nw = [], [], 0
+        recs, sigs = [], []  # merge-enabled sets also get the signatures
         for receiver, store, levels in items:
+            if self.merge_enabled and (levels is None or 0 in levels):
+                with store.lock:
+                    own = store.m.get(0)
+                if own is not None:
+                    recs.append((receiver, 0, 0, len(sigs)))
+                    sigs.append(own.sig[:64])
+                if levels is not None:
+                    levels = [lv for lv in levels if lv != 0]
             for level in (store.levels if levels is None else sorted(set(levels))):
                 size = store.size(level)
                 if size <= 0:
@@ -100,6 +119,16 @@ class DeviceStores(Stores):
                 with store.lock:
                     best = store.m.get(level)
                     indiv = store.indiv_verified.get(level, 0)
+                    held = dict(store.indiv_sigs.get(level, {})) if self.merge_enabled else {}
+                if self.merge_enabled:
+                    if best is not None:
+                        recs.append((receiver, level, HG_STORE_SIG_BEST, len(sigs)))
+                        sigs.append(best.sig[:64])
+                    pushed = self._pushed.setdefault((receiver, level), set())
+                    for idx in sorted(set(held) - pushed):
+                        recs.append((receiver, level, idx, len(sigs)))
+                        sigs.append(held[idx].sig[:64])
+                        pushed.add(idx)
                 lw = (size + 63) // 64
                 best_off = nw
                 if best is not None:
@@ -110,6 +139,8 @@ class DeviceStores(Stores):
                 nw += lw
         if ups:
             self.update(np.array(ups, dtype=STORE_UPDATE_DTYPE), np.concatenate(words))
+        if recs:  # after the update: it clears a level's "best signature known" bit
+            self.update_sigs(np.array(recs, dtype=STORE_SIG_DTYPE), b"".join(sigs))
 
 
 class DeviceIntake:
@@ -127,10 +158,17 @@ class DeviceIntake:
     (each as an entry of its own whose packet is parsed again; a pool of parsed
     slots kept in HBM across steps is not part of this). Each receiver has the reference's
     IndividualSigFilter (processing.go:299-325): an origin's individual
-    signature is presented once."""
+    signature is presented once.
+
+    device_merge=True: the picks are merged where they lie
+    (hg_stores_merge_device, on the same stream, after the verification); no
+    `Store.store`, no `combine_g1`, no `mirror`. Only the merge results, the
+    verdicts, scores, parse codes and the list of changed levels come back
+    (`last_results`, `last_changed`); the host stores in `host` stay empty, and
+    `best` / `combined` / `full_signature` read the device."""
 
     def __init__(self, engine: Engine, receivers: Sequence[int], k: int, max_packets: int = 4096,
-                 combine: Optional[Callable[[bytes, bytes], bytes]] = None):
+                 combine: Optional[Callable[[bytes, bytes], bytes]] = None, device_merge: bool = False):
         if k < 1:
             raise ValueError("k must be >= 1")
         self.engine, self.k, self.max_packets = engine, int(k), int(max_packets)
@@ -138,6 +176,11 @@ class DeviceIntake:
         self.n = int(engine.L.hg_registry_size(engine.ctx))
         self.stores = DeviceStores(engine, self.receivers, self.max_packets, self.n)
         self.stride = self.stores.stride
+        self.device_merge = bool(device_merge)
+        if self.device_merge:
+            self.stores.enable_merge()
+        self.last_results: List[int] = []               # HG_MERGE_* per pick of the last step
+        self.last_changed: List[Tuple[int, int]] = []   # (receiver, level) whose best the last step changed
         combine = combine or (lambda a, b: engine.combine_g1(a, b)[0])
         self.host: Dict[int, Store] = {r: Store(r, self.n, combine) for r in self.receivers}
         self.filters: Dict[int, IndividualSigFilter] = {r: IndividualSigFilter() for r in self.receivers}
@@ -147,6 +190,41 @@ class DeviceIntake:
 
     def close(self):
         self.stores.close()
+
+    def set_own(self, receiver: int, sig: bytes) -> None:
+        """The receiver's own signature, its level 0 (handel.go:116)."""
+        if self.device_merge:
+            self.stores.update_sigs(np.array([(receiver, 0, 0, 0)], dtype=STORE_SIG_DTYPE), bytes(sig[:64]))
+        else:
+            self.host[receiver].store_own(sig)
+
+    def best(self, receiver: int, level: int) -> Optional[MultiSig]:
+        """store.go:231-236 Best of one level (0: the own signature)."""
+        if not self.device_merge:
+            return self.host[receiver].best(level)[0]
+        words, sig, flags = self.stores.read_best(receiver, level)
+        if not flags & HG_STORE_HAS_BEST:
+            return None
+        if not flags & HG_STORE_BEST_SIG:
+            raise HandelGPUError("the level's best signature is not on the device")
+        lo, hi = part.range_level(receiver, self.n, level)
+        return MultiSig(hi - lo, int.from_bytes(words.astype("<u8").tobytes(), "little"), sig)
+
+    def combined(self, receiver: int, level: int) -> Optional[MultiSig]:
+        """store.go:248-262 Combined(level); level None: FullSignature (:238-246)."""
+        if not self.device_merge:
+            st = self.host[receiver]
+            return st.full_signature() if level is None else st.combined(level)
+        codes, bitlens, words, sigs = self.stores.combined(
+            [(receiver, HG_STORE_LEVEL_FULL if level is None else level)])
+        if codes[0] == HG_COMBINED_EMPTY:
+            return None
+        if codes[0] != HG_OK:
+            raise HandelGPUError(f"hg_stores_combined: query code {int(codes[0])}")
+        return MultiSig(int(bitlens[0]), int.from_bytes(words[0].astype("<u8").tobytes(), "little"), sigs[0].tobytes())
+
+    def full_signature(self, receiver: int) -> Optional[MultiSig]:
+        return self.combined(receiver, None)
 
     def _incoming(self, pkt: Packet, receiver: int, individual: bool) -> IncomingSig:
         lo, hi = part.range_level(receiver, self.n, pkt.level)
@@ -207,6 +285,13 @@ class DeviceIntake:
         # the whole capacity without reading the count first: the filler fails the level check
         eng.verify_aggregate_device(d_oreqs.data_ptr(), cap, d_words.data_ptr(), d_osigs.data_ptr(),
                                     d_vcodes.data_ptr(), stream=s)
+        if self.device_merge:
+            d_results = torch.empty(cap, dtype=torch.int32, device=dev)
+            d_changed = torch.empty(2 * cap, dtype=torch.int32, device=dev)
+            d_nchanged = torch.zeros(1, dtype=torch.int32, device=dev)
+            st.merge_device(d_pkts.data_ptr(), n, d_sel.data_ptr(), d_count.data_ptr(), cap, d_vcodes.data_ptr(),
+                            stride, d_words.data_ptr(), d_sigs.data_ptr(), d_results.data_ptr(),
+                            d_changed.data_ptr(), d_nchanged.data_ptr(), s)
         torch.cuda.synchronize(dev)
         count = int(d_count.cpu().numpy()[0])
         sel = d_sel.cpu().numpy()[:count].astype(np.int64)
@@ -217,11 +302,19 @@ class DeviceIntake:
             if pcodes[i] != HG_OK:
                 self.filters[batch[i][1]].seen.pop(batch[i][0].origin, None)
         results, changed = [], {}
-        for slot, code in zip(sel.tolist(), vcodes.tolist()):
+        if self.device_merge:
+            merged = d_results.cpu().numpy()[:count]
+            nch = int(d_nchanged.cpu().numpy()[0])
+            self.last_results = merged.tolist()
+            self.last_changed = [tuple(x) for x in d_changed.cpu().numpy()[:2 * nch].reshape(-1, 2).tolist()]
+        for e, (slot, code) in enumerate(zip(sel.tolist(), vcodes.tolist())):
             p, r = batch[slot % n][0], batch[slot % n][1]
             sp = self._incoming(p, r, slot >= n)
             err = None if code == HG_OK else eng.processing_error_string(int(code))
-            if err is None:
+            if self.device_merge:
+                if err is None and merged[e] not in (HG_MERGE_STORED, HG_MERGE_DISCARDED):
+                    err = f"device merge: result {int(merged[e])}"
+            elif err is None:
                 self.host[r].store(sp)
                 changed.setdefault(r, set()).add(sp.level)
             results.append((r, sp, err))

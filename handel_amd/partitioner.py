@@ -44,6 +44,63 @@ def range_level(node_id: int, size: int, level: int) -> Tuple[int, int]:
     return lo, min(hi, size)
 
 
+def range_level_inverse(node_id: int, size: int, level: int) -> Tuple[int, int]:
+    """binomialPartitioner.rangeLevelInverse (partitioner.go:185-211): [min, max)
+    of the ids that share `node_id`'s bits from `level - 1` up: the range the
+    peers at `level` expect a combined signature over. Raises PartitionerError
+    for an out-of-bound level."""
+    bitsize = log2_ceil(size)
+    if level < 0 or level > bitsize + 1:
+        raise PartitionerError("handel: invalid level for computing candidate set")
+    lo, hi = 0, 1 << bitsize
+    max_idx = level - 1
+    idx = bitsize - 1
+    while idx >= max_idx and idx >= 0 and lo < hi:
+        middle = (hi + lo) // 2
+        if (node_id >> idx) & 1:
+            lo = middle
+        else:
+            hi = middle
+        idx -= 1
+    return lo, min(hi, size)
+
+
+def _combine_size(sigs, bitlen: int, offset_of, combine_sigs) -> Tuple[int, int, bytes]:
+    """binomialPartitioner.combineSize (partitioner.go:282-296): every
+    signature's bits at its offset in a `bitlen`-bit set (an int, bit i = slot
+    i), the signatures folded with `combine_sigs` in the order given."""
+    bits, sig = 0, None
+    for s in sigs:
+        off = offset_of(s)
+        if off < 0 or off + s.ms.bitlen > bitlen:
+            raise PartitionerError("bitset: set out of bounds")  # WilffBitSet.Set panics (bitset.go:88-93)
+        bits |= s.ms.bits << off
+        sig = s.ms.sig if sig is None else combine_sigs(sig, s.ms.sig)
+    return bitlen, bits, sig
+
+
+def combine(node_id: int, size: int, sigs: Sequence, level: int, combine_sigs) -> Optional[Tuple[int, int, bytes]]:
+    """binomialPartitioner.Combine (partitioner.go:224-261): the signatures of
+    levels <= `level` (objects with .level and .ms: bitlen, bits, sig) as one
+    (bit length, bits, signature) over rangeLevelInverse(level); None for no
+    signatures, a signature above `level` or an invalid level."""
+    if not sigs or any(s.level > level for s in sigs):
+        return None
+    try:
+        gmin, gmax = range_level_inverse(node_id, size, level)
+    except PartitionerError:
+        return None
+    return _combine_size(sigs, gmax - gmin, lambda s: range_level(node_id, size, s.level)[0] - gmin, combine_sigs)
+
+
+def combine_full(node_id: int, size: int, sigs: Sequence, combine_sigs) -> Optional[Tuple[int, int, bytes]]:
+    """binomialPartitioner.CombineFull (partitioner.go:263-278): every
+    signature at its level's min in a registry-size bitset; None for none."""
+    if not sigs:
+        return None
+    return _combine_size(sigs, size, lambda s: range_level(node_id, size, s.level)[0], combine_sigs)
+
+
 def level_sizes(node_id: int, size: int) -> List[Tuple[int, int, int]]:
     """(level, min, max) for every non-empty level 1..log2(size) (Partitioner.Levels)."""
     out = []

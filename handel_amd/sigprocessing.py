@@ -259,6 +259,32 @@ class Store:
             ms = self.m.get(level)
             return ms, ms is not None
 
+    def store_own(self, sig: bytes) -> Optional[MultiSig]:
+        """The node's own signature as level 0 (handel.go:116: one bit, one signature)."""
+        return self.store(IncomingSig(self.node_id, 0, MultiSig(1, 1, bytes(sig))))
+
+    def max_level(self) -> int:
+        """binomialPartitioner.MaxLevel (partitioner.go:74-76)."""
+        return part.log2_ceil(self.n)
+
+    def combined(self, level: int) -> Optional[MultiSig]:
+        """store.go:248-262 Combined: the bests of levels <= `level` (level 0,
+        the own signature, included) as one multisignature over the range the
+        peers of level + 1 expect; None when there is none."""
+        with self.lock:
+            sigs = [IncomingSig(-1, k, ms) for k, ms in sorted(self.m.items()) if k <= level]
+        if level < self.max_level():
+            level += 1
+        r = part.combine(self.node_id, self.n, sigs, level, self.combine)
+        return None if r is None else MultiSig(*r)
+
+    def full_signature(self) -> Optional[MultiSig]:
+        """store.go:238-246 FullSignature: every level's best in a registry-size bitset."""
+        with self.lock:
+            sigs = [IncomingSig(-1, k, ms) for k, ms in sorted(self.m.items())]
+        r = part.combine_full(self.node_id, self.n, sigs, self.combine)
+        return None if r is None else MultiSig(*r)
+
 
 # ---------------------------------------------------------------------------
 # batched evaluator processing (processing.go:91-287)

@@ -351,6 +351,10 @@ int hg_packet_error(hg_ctx* ctx, int code, const hg_packet* p, char* buf, size_t
  * store stays authoritative: Store / unsafeCheckMerge (store.go:82-226) run on
  * the host once per verified signature, and the levels that changed are pushed
  * with hg_stores_update; only the scoring of queued signatures runs here.
+ * That is the default. A set that called hg_stores_enable_merge (the section
+ * after this one) also holds the signatures and runs Store / unsafeCheckMerge
+ * and Combined / FullSignature on the device; the host store is then a mirror
+ * a caller may keep or drop.
  * A store set belongs to the registry its context held at hg_stores_create:
  * after a later hg_registry_load every call returns HG_ERR_ARG. Every call
  * is a submission of the context (ordered with parse and verify across
@@ -418,6 +422,109 @@ size_t hg_stores_select_capacity(hg_stores* st, size_t n, uint32_t k);
 int hg_stores_select_device(hg_stores* st, const hg_packet* d_pkts, size_t n, const int32_t* d_scores, uint32_t k,
                             const hg_request* d_reqs, const uint8_t* d_sigs, uint32_t* d_sel, uint32_t* d_count,
                             hg_request* d_out_reqs, uint8_t* d_out_sigs, void* stream);
+
+/* ---------------------------------------------------------------- stores: merge and Combined
+ * Opt-in: the whole replace store on the device. After hg_stores_enable_merge
+ * the set also holds, beside the bitsets above, the 64-byte marshal of every
+ * level's best signature with a "best signature known" bit (HG_STORE_BEST_SIG
+ * in the level's flags), the node's own signature as level 0 (handel.go:116:
+ * one bit, one signature), every verified individual signature (store.go:58
+ * individualSigs; one table of registry-size entries per store, entry = the
+ * signer's registry id, the store's own id holding level 0) and a "signature
+ * held" bitset per level. hg_stores_merge_device is then store.go:82-99 Store
+ * (unsafeCheckMerge :188-229 + store :264-269) for the verified picks of an
+ * intake step, and hg_stores_combined* store.go:238-262 FullSignature /
+ * Combined (partitioner.go:224-296 Combine / CombineFull). A caller that runs
+ * the merge here no longer runs Store / unsafeCheckMerge on the host; a set
+ * that never calls hg_stores_enable_merge behaves and allocates as before, and
+ * on it the entry points below (hg_stores_enable_merge apart) return
+ * HG_ERR_ARG. Every signature that leaves the device is the marshal
+ * SigBLS.MarshalBinary gives (bn256/go/bn256.go:170-172; infinity: 64 zero
+ * bytes). Signatures are not checked here: they are verified ones, or the
+ * caller's own. */
+#define HG_STORE_BEST_SIG 2u /* level flags: the best's signature is held (cleared by hg_stores_update) */
+#define HG_STORE_SIG_BEST 0xffffffffu   /* hg_store_sig.index: the level's best signature */
+#define HG_STORE_LEVEL_FULL 0xffffffffu /* hg_store_query.level: FullSignature */
+typedef struct {
+  uint32_t receiver; /* a hosted receiver id */
+  uint32_t level;    /* 0: the own signature (index ignored); else one of the receiver's non-empty levels */
+  uint32_t index;    /* mapped index at the level (id - level min): an individual signature; HG_STORE_SIG_BEST */
+  uint32_t sig_off;  /* the signature: sigs[64 * sig_off ...] */
+} hg_store_sig;
+typedef struct {
+  uint32_t receiver; /* a hosted receiver id */
+  uint32_t level;    /* 0 .. ceil(log2 N) - 1: Combined(level); HG_STORE_LEVEL_FULL */
+} hg_store_query;
+/* hg_stores_merge_device's result per entry */
+enum {
+  HG_MERGE_SKIPPED = 0,        /* verdict not HG_OK, or a filler entry */
+  HG_MERGE_STORED = 1,         /* the level's best is now this entry's merge (store.go:95-97) */
+  HG_MERGE_DISCARDED = 2,      /* unsafeCheckMerge returned false (store.go:211-213) */
+  HG_MERGE_ERR_MISSING = 3,    /* a needed best or individual signature is not held (store.go:219 panics) */
+  HG_MERGE_ERR_INDIVIDUAL = 4, /* an individual slot whose bitset is not its one bit (store.go:87-89 panics) */
+  HG_MERGE_ERR_ROW = 5         /* the slot's packet names no (store, level) of this set */
+};
+/* hg_stores_combined*'s code per query (HG_OK, HG_ERR_ARG: the level is neither
+ * below ceil(log2 N) nor HG_STORE_LEVEL_FULL, the receiver is not hosted, or
+ * the bitset does not fit words_stride) */
+#define HG_COMBINED_EMPTY 1       /* no best at those levels: the reference returns nil (partitioner.go:225-227) */
+#define HG_COMBINED_ERR_MISSING 2 /* a level has a best whose signature is not held */
+/* Allocates the signature tables (idempotent). Levels that already have a best
+ * (hg_stores_update) keep it without a signature until hg_stores_update_sigs
+ * gives one. */
+int hg_stores_enable_merge(hg_stores* st);
+/* Loads n signatures from the host (seeding, and a host store's mirror), each
+ * target named at most once: an individual signature (sets its "held" bit, not
+ * the verified bit: that is hg_stores_update's bitset), a level's best
+ * signature (sets HG_STORE_BEST_SIG), or the own signature (level 0; it is the
+ * level-0 best, crypto.go / handel.go:116). sigs holds n_sigs 64-byte
+ * marshals. Synchronous. */
+int hg_stores_update_sigs(hg_stores* st, const hg_store_sig* recs, size_t n, const uint8_t* sigs, size_t n_sigs);
+/* Reads one level back (store.go:231-236 Best): best receives
+ * hg_packet_stride_words words, sig the best's 64-byte marshal, *flags
+ * HG_STORE_HAS_BEST | HG_STORE_BEST_SIG as they hold (each nullable). Level 0:
+ * word 0 bit 0 and both flags say whether the own signature is held. */
+int hg_stores_read_best(hg_stores* st, uint32_t receiver, uint32_t level, uint64_t* best, uint8_t* sig, int* flags);
+/* store.go:82-99 Store for the picks of one intake step. d_sel[e] names the
+ * slot of entry e (hg_stores_select_device's output; >= 2n: a filler),
+ * d_vcodes[e] its verdict (hg_verify_aggregate_device); entries e <
+ * min(*d_count, capacity), or all `capacity` with d_count NULL. d_pkts[n],
+ * d_words (slot * stride_words) and d_sigs (slot * 64) are the parse outputs.
+ * The entries whose verdict is HG_OK are applied to their (receiver, level) in
+ * array order; every level ends in the state the reference's store reaches
+ * when fed those entries in that order: an individual slot (>= n) first sets
+ * its verified bit and keeps its signature (store.go:86-92); then
+ * unsafeCheckMerge: without a best the entry becomes the best; else the
+ * candidate is the union with the best and the G1 sum of both signatures
+ * (bn256/go/bn256.go:192-200 Combine) when the two sets are disjoint, the
+ * entry itself otherwise; with iS the verified individual signatures outside
+ * the candidate, the entry is discarded when |iS| + |candidate| <= |best|,
+ * else every signature of iS joins the candidate, which becomes the best.
+ * An entry that ends in an error changes nothing. d_results[capacity]: HG_MERGE_*
+ * (entries past the count: HG_MERGE_SKIPPED). d_changed[2 * capacity]:
+ * (receiver, level) of the levels whose best changed, ordered by their first
+ * entry, *d_nchanged of them. n <= max_packets, capacity <= 2 * max_packets,
+ * stride_words >= hg_packet_stride_words, d_sigs 4-byte aligned. Asynchronous
+ * on `stream`. */
+int hg_stores_merge_device(hg_stores* st, const hg_packet* d_pkts, size_t n, const uint32_t* d_sel,
+                           const uint32_t* d_count, size_t capacity, const int32_t* d_vcodes, size_t stride_words,
+                           const uint64_t* d_words, const uint8_t* d_sigs, int32_t* d_results, uint32_t* d_changed,
+                           uint32_t* d_nchanged, void* stream);
+/* store.go:248-262 Combined(level) / :238-246 FullSignature for m queries, all
+ * pointers on the device. Combined(level): the bests of levels <= level, level
+ * 0 included, each at rangeLevel(k).min - rangeLevelInverse(level + 1).min in
+ * a bitset of rangeLevelInverse(level + 1)'s size (partitioner.go:185-211,
+ * 224-261), their signatures summed; HG_STORE_LEVEL_FULL: every level at its
+ * rangeLevel min in a registry-size bitset (:263-278). Per query q:
+ * d_codes[q], d_bitlens[q], d_words[q * words_stride ...] (words_stride words,
+ * zero above the bit length) and d_sigs[64 * q ...]; a query whose code is not
+ * HG_OK leaves zero words and a zero signature. Asynchronous on `stream`. */
+int hg_stores_combined_device(hg_stores* st, const hg_store_query* d_queries, size_t m, size_t words_stride,
+                              int32_t* d_codes, uint32_t* d_bitlens, uint64_t* d_words, uint8_t* d_sigs,
+                              void* stream);
+/* The same with host pointers. Synchronous. */
+int hg_stores_combined(hg_stores* st, const hg_store_query* queries, size_t m, size_t words_stride, int32_t* codes,
+                       uint32_t* bitlens, uint64_t* words, uint8_t* sigs);
 
 /* ---------------------------------------------------------------- batcher
  * A launch-merging request queue on one context, for callers that verify one

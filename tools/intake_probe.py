@@ -10,7 +10,18 @@ one stream, several windows after a warm-up.
 
 Bytes are the algorithm's: 3 x stride x 8 per slot that is scored against a
 store (the slot's bitset, the level's best, its verified individual
-signatures). Needs a GPU: there is no fallback.
+signatures).
+
+The same run also times the opt-in device store at this shape
+(hg_stores_enable_merge): (a) hg_stores_merge_device over the selection with
+every pick verified, each timed call on the freshly mirrored state (a repeated
+call on the merged state, where nearly every entry is discarded, is given
+beside it); (b) the host tail it replaces on the default DeviceIntake path,
+Store.store with Engine.combine_g1 for every pick plus mirror_many of the
+changed levels; (c) hg_stores_combined_device for all receivers x levels
+against Store.combined in a host loop. Device and host states, and every
+Combined, are asserted equal before anything is reported. Needs a GPU: there is
+no fallback.
 """
 
 import argparse
@@ -78,6 +89,156 @@ def make_case(seed=7):
         reqs[i] = reqs[n + i] = (lo, size, size, 0)
         reqs[i]["word_offset"], reqs[n + i]["word_offset"] = i * stride, (n + i) * stride
     return receivers, host, pkts, reqs, words, codes, sps, stride
+
+
+def merge_probe(a, e, st, host, receivers, pkts, words, sps, stride, d_pkts, d_words, d_sel, d_count, cap, dev, stream,
+                timed, up):
+    """(a), (b), (c) of the module text on the selection d_sel / d_count holds;
+    `st` (the default, scoring-only set) takes the host tail's mirror."""
+    import torch
+
+    import bench
+    from handel_amd import partitioner as HP
+    from handel_amd._lib import HG_MERGE_DISCARDED, HG_MERGE_STORED, HG_STORE_BEST_SIG, HG_STORE_HAS_BEST
+    from handel_amd.engine import STORE_QUERY_DTYPE
+    from handel_amd.intake import DeviceStores
+    from handel_amd.sigprocessing import IncomingSig, MultiSig, Store
+
+    n, s = N_PKTS, stream.cuda_stream
+    top = HP.log2_ceil(N_REG)
+    # real, distinct points: every slot its own, the seeded state's drawn from a pool by position
+    slot_sigs = e.sign(bench.seeded_scalars(2 * n, 4001))
+    pool_b = e.sign(bench.seeded_scalars(4096, 4002))
+    pool = [pool_b[64 * i:64 * i + 64] for i in range(4096)]
+    own = e.sign(bench.seeded_scalars(N_REG, 4000))
+    combine = lambda x, y: e.combine_g1(x, y)[0]  # noqa: E731
+    host2 = {}
+    for r in receivers:
+        h = Store(r, N_REG, combine)
+        h.store_own(own[64 * r:64 * r + 64])
+        for lv in h.levels:
+            size = h.size(lv)
+            cur = host[r].m.get(lv)
+            if cur is not None:
+                h.m[lv] = MultiSig(size, cur.bits, pool[(r * 31 + lv) % 4096])
+            iv = host[r].indiv_verified[lv]
+            h.indiv_verified[lv] = iv
+            for idx in range(size):
+                if (iv >> idx) & 1:
+                    h.indiv_sigs[lv][idx] = MultiSig(size, 1 << idx, pool[(r * 131 + lv * 17 + idx) % 4096])
+        host2[r] = h
+    stm = DeviceStores(e, receivers, n)
+    stm.enable_merge()
+    count = int(d_count.cpu()[0])
+    sel = d_sel.cpu().numpy().view(np.uint32)[:count].tolist()
+    d_sigs2 = up(np.frombuffer(slot_sigs, dtype=np.uint8))
+    d_ok = torch.zeros(cap, dtype=torch.int32, device=dev)  # every pick verified: the most merge work
+    d_results = torch.zeros(cap, dtype=torch.int32, device=dev)
+    d_changed = torch.zeros(2 * cap, dtype=torch.int32, device=dev)
+    d_nchanged = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def merge():
+        stm.merge_device(d_pkts.data_ptr(), n, d_sel.data_ptr(), d_count.data_ptr(), cap, d_ok.data_ptr(), stride,
+                         d_words.data_ptr(), d_sigs2.data_ptr(), d_results.data_ptr(), d_changed.data_ptr(),
+                         d_nchanged.data_ptr(), s)
+
+    # (a) one call per window on the mirrored pre-state (a merged state would discard nearly everything)
+    first_ms = []
+    for w in range(a.windows + 1):  # the first window is the warm-up
+        stm.mirror_many([(r, host2[r], None) for r in receivers])
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        merge()
+        e1.record(stream)
+        e1.synchronize()
+        if w:
+            first_ms.append(e0.elapsed_time(e1))
+    results = d_results.cpu().numpy()[:count].tolist()
+    nchanged = int(d_nchanged.cpu()[0])
+    # the device state after that one merge, read before anything else touches it
+    as_int = lambda w: int.from_bytes(w.astype("<u8").tobytes(), "little")  # noqa: E731
+    device_rows = {}
+    for r in receivers:
+        for lv in host2[r].levels:
+            best, sig, flags = stm.read_best(r, lv)
+            device_rows[(r, lv)] = (as_int(best), sig, flags, as_int(stm.read(r, lv)[1]))
+
+    # (c) Combined of every receiver and level, on the same state
+    queries = np.array([(r, lv) for r in receivers for lv in range(top)], dtype=STORE_QUERY_DTYPE)
+    m, ws = len(queries), (N_REG + 63) // 64
+    d_q = up(queries)
+    d_qcodes = torch.zeros(m, dtype=torch.int32, device=dev)
+    d_qbits = torch.zeros(m, dtype=torch.int32, device=dev)
+    d_qwords = torch.zeros(m * ws, dtype=torch.int64, device=dev)
+    d_qsigs = torch.zeros(m * 64, dtype=torch.uint8, device=dev)
+
+    def combined():
+        stm.combined_device(d_q.data_ptr(), m, ws, d_qcodes.data_ptr(), d_qbits.data_ptr(), d_qwords.data_ptr(),
+                            d_qsigs.data_ptr(), s)
+
+    for _ in range(3):
+        combined()
+    comb_ms = timed(combined, max(20, a.reps // 10))
+    torch.cuda.synchronize(dev)
+    qcodes, qbits = d_qcodes.cpu().numpy(), d_qbits.cpu().numpy()
+    qwords = d_qwords.cpu().numpy().view(np.uint64).reshape(m, ws)
+    qsigs = d_qsigs.cpu().numpy().reshape(m, 64)
+
+    # the same entries again: the merged state discards nearly all of them (the call's floor)
+    repeat_ms = timed(merge, max(20, a.reps // 10))
+    torch.cuda.synchronize(dev)
+
+    # (b) the host tail of the default path on the same picks
+    t0 = time.perf_counter()
+    changed, want_results = {}, []
+    for slot in sel:
+        r, sp = sps[slot]
+        sp = IncomingSig(sp.origin, sp.level, MultiSig(sp.ms.bitlen, sp.ms.bits, slot_sigs[64 * slot:64 * slot + 64]),
+                         ind=sp.ind, mapped_index=sp.mapped_index)
+        kept = host2[r].store(sp)
+        want_results.append(HG_MERGE_STORED if kept is not None else HG_MERGE_DISCARDED)
+        changed.setdefault(r, set()).add(sp.level)
+    t1 = time.perf_counter()
+    st.mirror_many([(r, host2[r], lv) for r, lv in changed.items()])
+    t2 = time.perf_counter()
+    states_equal = results == want_results
+    for r in receivers:
+        for lv in host2[r].levels:
+            best, sig, flags, indiv = device_rows[(r, lv)]
+            want = host2[r].m.get(lv)
+            ok = bool(flags & HG_STORE_HAS_BEST) == (want is not None)
+            if ok and want is not None:
+                ok = bool(flags & HG_STORE_BEST_SIG) and sig == want.sig and best == want.bits
+            states_equal = states_equal and ok and indiv == host2[r].indiv_verified[lv]
+    t3 = time.perf_counter()
+    want_comb = [host2[int(r)].combined(int(lv)) for r, lv in queries]
+    t4 = time.perf_counter()
+    combined_equal = all(
+        qcodes[q] == 0 and (int(qbits[q]), int.from_bytes(qwords[q].astype("<u8").tobytes(), "little"),
+                            qsigs[q].tobytes()) == (ms.bitlen, ms.bits, ms.sig)
+        for q, ms in enumerate(want_comb))  # every store holds its own signature: never empty
+    stm.close()
+    fm, rm, cm = statistics.median(first_ms), statistics.median(repeat_ms), statistics.median(comb_ms)
+    rec = {
+        "merge_what": "hg_stores_merge_device over the selection, every pick verified; hg_stores_combined_device for all "
+                      "receivers x levels; host: Store.store / Store.combined with Engine.combine_g1",
+        "merge_entries": count, "merge_stored": results.count(HG_MERGE_STORED),
+        "merge_discarded": results.count(HG_MERGE_DISCARDED), "merge_rows_changed": nchanged,
+        "merge_states_equal_host": bool(states_equal),
+        "merge_first_ms": {"median": fm, "min": min(first_ms), "max": max(first_ms), "calls_per_window": 1},
+        "merge_repeat_ms": {"median": rm, "min": min(repeat_ms), "max": max(repeat_ms)},
+        "host_tail_s": {"store": t1 - t0, "mirror_many": t2 - t1, "total": t2 - t0},
+        "merge_device_over_host_tail": (t2 - t0) * 1e3 / fm,
+        "combined_queries": m, "combined_equal_host": bool(combined_equal),
+        "combined_ms": {"median": cm, "min": min(comb_ms), "max": max(comb_ms)},
+        "host_combined_s": t4 - t3,
+        "combined_device_over_host": (t4 - t3) * 1e3 / cm,
+    }
+    if not (states_equal and combined_equal):
+        print(json.dumps(rec))
+        sys.exit("device store differs from the host Store")
+    return rec
 
 
 def main():
@@ -173,6 +334,9 @@ def main():
     ver_ms = timed(verify, max(20, a.reps // 10))
     torch.cuda.synchronize(dev)
 
+    merge_rec = merge_probe(a, e, st, host, receivers, pkts, words, sps, stride, d_pkts, d_words, d_sel, d_count, cap,
+                            dev, stream, timed, up)
+
     ev, bo, ve, hs = statistics.median(ev_ms), statistics.median(both_ms), statistics.median(ver_ms), min(host_s)
     nbytes = len(scored) * 3 * stride * 8
     rec = {
@@ -193,6 +357,7 @@ def main():
         "device_over_host": (hs * 1e3) / ev,
         "device_select_over_host": (hs * 1e3) / bo,
     }
+    rec.update(merge_rec)
     st.close()
     e.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
