@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64) void k_decode_g2(const uint8_t* bytes, int n, i
 // n * key != inf (on the twist but outside the order-n subgroup G2). x/crypto's
 // G2.Unmarshal (bn256/go/bn256.go:113-120) accepts such keys; the GT path's
 // bilinearity argument only holds on G2, so a registry holding one is served
-// by the G2 fold + two-pairing check instead (hg_api.cpp gt_max_level).
+// by the G2 fold + two-pairing check instead (hg_aggregate.cpp gt_max_level).
 __global__ __launch_bounds__(64) void k_g2_subgroup(const PointG2* reg, int n, int* count) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
