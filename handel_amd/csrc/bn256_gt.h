@@ -1,6 +1,7 @@
 // bn256_gt.h — data of the GT aggregate-verification path (bn256_gt.hip).
 #pragma once
 #include "bn256_kernels.h"
+#include "bn256_sigform.h"
 
 namespace hg {
 
@@ -66,38 +67,20 @@ void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_
 void launch_verify_sig(const PointG1* sigs, int n, const LineCoef* tab, const Gt* y, int32_t* codes, hipStream_t s);
 // the same check in two launches, so the fold can run beside the pairing:
 // fe[r] = FE(Miller(G2Base at -sig_r)) from the 64-byte marshals (decoded in
-// the kernel), then fe[r] == y[r] where still HG_OK
-// k_verify_sig_split<2>: a check's team spread over two waves (the latency
-// form, bn256_sigsplit.h); a padded launch_sig_pairing of n <= min(w2_max,
-// 2048) checks takes it unless HG_SIG_W2=0. sig_w2_lane_max: the bound for
-// lanes (HG_SIG_W2_LANE_MAX, 0)
-static constexpr int kSigW2MaxN = 2048;
-bool sig_w2_for(bool pad, int n, int w2_max);
-int sig_w2_lane_max();
-void launch_sig_pairing_w2(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s);
-void launch_sig_pairing(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s,
-                        bool pad = true, int w2_max = kSigW2MaxN);
-// launch_sig_pairing on five 12-lane teams per wave (bn256_sig12.hip): the
-// lines evaluated at -sig first (k_sig_lines, into ev: sig12_lines_bytes(n)),
-// then k_verify_sig12; the same fe values
-size_t sig12_lines_bytes(int n);
-void launch_sig_pairing12(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Fp* ev, Gt* fe,
-                          hipStream_t s, bool pad);
-// which kernel a submission runs: the 12-lane one for unpadded launches (the
-// throughput mode: batches in flight share the SIMDs, and a check costs 20 %
-// fewer wave-instructions), the 16-lane padded k_verify_sig for padded ones
-// (the latency mode: one wave per SIMD, where its shorter per-wave program
-// and the absence of the line kernels give the lower batch latency).
-// HG_SIG12=1 / 0 forces one kernel for every launch (A/B).
-// n: the batch's checks; above kSig12MaxN the 12-lane path (whose line kernel
-// indexes 4 n threads in int) is never taken
-constexpr int kSig12MaxN = 1 << 28;
-bool sig12_for(bool pad, size_t n = 0);
+// the kernel), then fe[r] == y[r] where still HG_OK (launch_gt_compare).
+// Which of the pairing's forms a batch runs, and why, is bn256_sigform.h's
+// sig_form(); these run it. sig_env: the A/B knobs, read once.
+// ws: sig_form_ws_bytes(f, n) bytes (bn256_sigform.h; none for most forms).
+// launch_sig_form: false, with nothing launched, for a 12-lane form above
+// kSig12MaxN (HG_ERR_ARG to the caller: the codes must not stay HG_OK).
+const SigEnv& sig_env();
+bool launch_sig_form(SigForm f, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws, Gt* fe,
+                     hipStream_t s);
 // the split chain's final exponentiation (k_sig12_norm, k_sig12_ninv,
 // k_sig12_fe) of n Miller values in fe, in place: config 2's second half
-// (launch_verify_split); ws: fe12_ws_bytes(n) bytes
+// (launch_verify_split); ws: fe12_ws_bytes(n) bytes. false as launch_sig_form
 size_t fe12_ws_bytes(int n);
-void launch_fe12(Gt* fe, int n, uint8_t* ws, hipStream_t s);
+bool launch_fe12(Gt* fe, int n, uint8_t* ws, hipStream_t s);
 void launch_gt_compare(const Gt* fe, const Gt* y, int n, int32_t* codes, hipStream_t s);
 // the same, and the verdict bitset (ceil(n / 8) bytes, hg_pack_verdicts_device's layout)
 void launch_gt_compare_bits(const Gt* fe, const Gt* y, int n, int32_t* codes, uint8_t* bits, hipStream_t s);

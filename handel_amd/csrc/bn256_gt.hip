@@ -512,8 +512,8 @@ __global__ __launch_bounds__(64) void k_gt_combine(int n, const GtHdr* hdr, cons
 // the side stream, off this kernel's critical path. A signature that fails to
 // decode gives a meaningless FE value, which k_gt_compare never reads (its code
 // is the decode error already).
-// kPad: one pairing wave per SIMD (below); HG_SIG_PAD=0 launches the
-// unpadded variant, two waves per SIMD when two batches are in flight
+// kPad: one pairing wave per SIMD (below); SigForm::W16 is the unpadded
+// variant, two waves per SIMD when two batches are in flight
 template <int TEAMS, bool kStore, bool kPad = (TEAMS == 4)>
 __global__ __launch_bounds__(64) void k_verify_sig(const PointG1* sigs, const uint8_t* sig_bytes, int flavor, int n,
                                                    const LineCoef* tab, const Gt* y, Gt* fe, int32_t* codes) {
@@ -627,51 +627,47 @@ void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_
 void launch_verify_sig(const PointG1* sigs, int n, const LineCoef* tab, const Gt* y, int32_t* codes, hipStream_t s) {
   if (n > 0) k_verify_sig<4, false><<<nblk(n, 4), 64, 0, s>>>(sigs, nullptr, 0, n, tab, y, nullptr, codes);
 }
-// pad (the default): one pairing wave per SIMD (k_verify_sig above); lanes
-// that keep two batches in flight launch the unpadded variant, so the second
-// batch's waves share the SIMDs. Experiment knobs (A/B): HG_SIG_TEAMS=2 — two
-// checks per wave, unpadded; HG_SIG_PAD=0/1 — overrides `pad`.
-static int sig_env() {
-  static const int v = [] {
-    const char* t = getenv("HG_SIG_TEAMS");
-    if (t && atoi(t) == 2) return 2;
-    const char* p = getenv("HG_SIG_PAD");
-    if (!p) return -1;
-    return atoi(p) == 0 ? 0 : 1;
+// HG_SIG12, HG_SIG12_SPLIT, HG_SIG_W2, HG_SIG_W2_LANE_MAX, HG_VERIFY_SPLIT
+// (bn256_sigform.h SigEnv): the one place that reads them
+const SigEnv& sig_env() {
+  static const SigEnv env = [] {
+    auto on = [](const char* name, bool def) {
+      const char* e = getenv(name);
+      return e ? atoi(e) != 0 : def;
+    };
+    SigEnv v;
+    if (getenv("HG_SIG12")) v.sig12 = on("HG_SIG12", false) ? 1 : 0;
+    v.sig12_split = on("HG_SIG12_SPLIT", true);
+    v.w2 = on("HG_SIG_W2", true);
+    if (const char* e = getenv("HG_SIG_W2_LANE_MAX")) v.w2_lane_max = atoi(e);
+    if (const char* e = getenv("HG_VERIFY_SPLIT")) v.verify_split = atoi(e) == 1;
+    return v;
   }();
-  return v;
+  return env;
 }
-// the two-wave teams for a padded launch of at most w2_max (<= kSigW2MaxN)
-// checks; HG_SIG_W2=0 turns them off (A/B)
-bool sig_w2_for(bool pad, int n, int w2_max) {
-  static const bool on = [] {
-    const char* e = getenv("HG_SIG_W2");
-    return !e || atoi(e) != 0;
-  }();
-  return on && pad && n <= w2_max && n <= kSigW2MaxN;
-}
-int sig_w2_lane_max() {
-  static const int v = [] {
-    const char* e = getenv("HG_SIG_W2_LANE_MAX");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-void launch_sig_pairing(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s,
-                        bool pad, int w2_max) {
-  if (n <= 0) return;
-  const int env = sig_env();
-  if (env < 0 && sig_w2_for(pad, n, w2_max)) {
-    launch_sig_pairing_w2(sigs, flavor, n, tab, fe, s);
-    return;
+// the 12-lane and two-wave bodies, in their own units (bn256_sig12.hip;
+// bn256_sigw2.hip, the only one built with HG_TEAM_SPLIT)
+bool launch_sig12(bool pad, bool split, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws,
+                  Gt* fe, hipStream_t s);
+void launch_sig_w2(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s);
+bool launch_sig_form(SigForm f, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws, Gt* fe,
+                     hipStream_t s) {
+  switch (f) {
+    case SigForm::W16Pad:
+      if (n > 0) k_verify_sig<4, true><<<nblk(n, 4), 64, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
+      return true;
+    case SigForm::W16:
+      if (n > 0)
+        k_verify_sig<4, true, false><<<nblk(n, 4), 64, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
+      return true;
+    case SigForm::T12Pad:
+    case SigForm::T12:
+      return launch_sig12(f == SigForm::T12Pad, sig_form_split(sig_env(), f), sigs, flavor, n, tab, ws, fe, s);
+    case SigForm::W2:
+      launch_sig_w2(sigs, flavor, n, tab, fe, s);
+      return true;
   }
-  if (env == 2) {
-    k_verify_sig<2, true><<<nblk(n, 2), 32, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
-    return;
-  }
-  if (env >= 0) pad = env == 1;
-  if (pad) k_verify_sig<4, true><<<nblk(n, 4), 64, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
-  else k_verify_sig<4, true, false><<<nblk(n, 4), 64, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
+  return false;
 }
 void launch_gt_compare(const Gt* fe, const Gt* y, int n, int32_t* codes, hipStream_t s) {
   if (n > 0) k_gt_compare<<<n, 64, 0, s>>>(fe, y, n, codes);

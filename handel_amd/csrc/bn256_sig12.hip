@@ -33,8 +33,6 @@
 // same order, canonical), so the FE values, and every verdict, are too.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "bn256_decode.h"
 #include "bn256_g2sched.h"
 #include "bn256_gt.h"
@@ -152,6 +150,43 @@ HG_DEV void team_miller_sig12(const Team& T, uint32_t* F, const Fp* ev, int n, i
   ILineT::run(T, S, after);
 }
 
+// What every 12-lane pairing kernel starts with, after its LDS array
+// (kSig12LdsWords words): its priority and kPad's padding, the wave's five
+// teams on layout T (F: its register
+// file) and the check each runs, idx (valid: idx < n; a padding team reads the
+// inputs of the last check, ci). Out-parameters, not a struct: returning one
+// moved the kernels' machine code.
+static constexpr int kSig12LdsWords = kTeams12 * kSigTTeamElems * 10;
+template <bool kPad>
+HG_DEV Team sig12_team(uint32_t* lds, int n, uint32_t*& F, int& idx, bool& valid, int& ci) {
+  // beside the GT fold on another stream: the pairing wave (the step's
+  // critical path) wins the issue arbitration
+  __builtin_amdgcn_s_setprio(3);
+  // one pairing wave per SIMD: an allocation above half the VGPR file
+  if constexpr (kPad) asm volatile("" ::: "v255", "a0");
+  Team T = make_team12(lds, kSigTTeamElems * 10);
+  F = T.base + kSigTRegBase * 10;
+  idx = blockIdx.x * kTeams12 + team12_index();
+  valid = idx < n;
+  ci = valid ? idx : n - 1;
+  return T;
+}
+
+// The final exponentiation's parking records (bn256_sigfe.h): res in fe[idx]
+// (the result overwrites it), t0 in park[idx]; a padding team (idx >= n) uses
+// the spare records park[n + 1 + (idx - n)] and park[n + 1 + kTeams12 +
+// (idx - n)] (park has n + 1 + 2 kTeams12 records, Sig12Layout). Recomputed
+// at each use.
+struct Sig12Park {
+  Gt *fe, *park;
+  int n;
+  HG_DEV uint32_t* operator()(int k) const {
+    const int i = blockIdx.x * kTeams12 + team12_index();
+    if (k == 0) return (i < n ? fe + i : park + n + 1 + (i - n))->w;
+    return (i < n ? park + i : park + n + 1 + kTeams12 + (i - n))->w;
+  }
+};
+
 // fe[r] = FE(Miller(G2Base at -sig_r)) on layout T (kSigTTeamElems elements
 // per team: 18.4 KB of LDS per wave), five teams per wave. The final
 // exponentiation parks two values per check in HBM: fe[r] itself (the result
@@ -159,28 +194,14 @@ HG_DEV void team_miller_sig12(const Team& T, uint32_t* F, const Fp* ev, int n, i
 // k_verify_sig's default); unpadded, two batches' waves share a SIMD.
 template <bool kPad>
 __global__ __launch_bounds__(64, kPad ? 1 : 2) void k_verify_sig12(const Fp* ev, int n, Gt* fe, Gt* park) {
-  constexpr int kWords = kSigTTeamElems * 10;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTeams12 * kWords];
-  // beside the GT fold on another stream: the pairing wave (the step's
-  // critical path) wins the issue arbitration
-  __builtin_amdgcn_s_setprio(3);
-  if constexpr (kPad) asm volatile("" ::: "v255", "a0");
-  Team T = make_team12(lds, kWords);
-  uint32_t* F = T.base + kSigTRegBase * 10;
-  const int idx = blockIdx.x * kTeams12 + team12_index();
-  const bool valid = idx < n;
-  const int ci = valid ? idx : n - 1;
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSig12LdsWords];
+  uint32_t* F;
+  int idx, ci;
+  bool valid;
+  Team T = sig12_team<kPad>(lds, n, F, idx, valid, ci);
   XStream S = x_stream();
   team_miller_sig12(T, F, ev, n, ci, S, SigFE<SigProgs12>::final_exp_hint_t());
-  // parking records: res in fe[idx] (the result overwrites it), t0 in
-  // park[idx]; a padding team (idx >= n) uses the spare records
-  // park[n + 1 + (idx - n)] and park[n + 1 + kTeams12 + (idx - n)] (park has
-  // n + 1 + 2 kTeams12 records, sig12_scalar_offset). Recomputed at each use.
-  SigFE<SigProgs12>::team_final_exp_fc_t(T, S, [=](int k) -> uint32_t* {
-    const int i = blockIdx.x * kTeams12 + team12_index();
-    if (k == 0) return (i < n ? fe + i : park + n + 1 + (i - n))->w;
-    return (i < n ? park + i : park + n + 1 + kTeams12 + (i - n))->w;
-  });
+  SigFE<SigProgs12>::team_final_exp_fc_t(T, S, Sig12Park{fe, park, n});
   team_sync();
   Fp v;
   ld_fp_a8(v, slot(T, S_F) + T.e * 10);
@@ -229,15 +250,11 @@ HG_DEV void sig12_store_terms(const Team& T, bool valid, const NormTerms& o, con
 template <bool kPad>
 __global__ __launch_bounds__(64, kPad ? 1 : 2) void k_sig12_miller(const Fp* ev, int n, Gt* fe, SigHand* hand,
                                                                    Fp* nrm) {
-  constexpr int kWords = kSigTTeamElems * 10;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTeams12 * kWords];
-  __builtin_amdgcn_s_setprio(3);
-  if constexpr (kPad) asm volatile("" ::: "v255", "a0");
-  Team T = make_team12(lds, kWords);
-  uint32_t* F = T.base + kSigTRegBase * 10;
-  const int idx = blockIdx.x * kTeams12 + team12_index();
-  const bool valid = idx < n;
-  const int ci = valid ? idx : n - 1;
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSig12LdsWords];
+  uint32_t* F;
+  int idx, ci;
+  bool valid;
+  Team T = sig12_team<kPad>(lds, n, F, idx, valid, ci);
   XStream S = x_stream();
   team_miller_sig12(T, F, ev, n, ci, S, xh<ISqr12T>());
   SigFE<SigProgs12>::fe_t_norm(T, S, xh_none());
@@ -279,14 +296,11 @@ HG_DEV void sig12_load_f(const Team& T, uint32_t* F, const Gt* fe, int ci) {
 // 2's k_verify_ml, bn256_verify.hip): f = fe[c], the norm N = f conj(f)
 // (fe_t_norm), then t12_inv_norm up to d: the terms -> hand[c], n -> nrm[c]
 __global__ __launch_bounds__(64, 2) void k_sig12_norm(int n, const Gt* fe, SigHand* hand, Fp* nrm) {
-  constexpr int kWords = kSigTTeamElems * 10;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTeams12 * kWords];
-  __builtin_amdgcn_s_setprio(3);
-  Team T = make_team12(lds, kWords);
-  uint32_t* F = T.base + kSigTRegBase * 10;
-  const int idx = blockIdx.x * kTeams12 + team12_index();
-  const bool valid = idx < n;
-  const int ci = valid ? idx : n - 1;
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSig12LdsWords];
+  uint32_t* F;
+  int idx, ci;
+  bool valid;
+  Team T = sig12_team<false>(lds, n, F, idx, valid, ci);
   XStream S = x_stream();
   sig12_load_f(T, F, fe, ci);
   SigFE<SigProgs12>::fe_t_norm(T, S, xh_none());
@@ -347,15 +361,11 @@ __global__ __launch_bounds__(kInvBlock) void k_sig12_ninv(const Fp* nrm, int n, 
 template <bool kPad>
 __global__ __launch_bounds__(64, kPad ? 1 : 2) void k_sig12_fe(int n, Gt* fe, Gt* park, const SigHand* hand,
                                                                const Fp* ninv) {
-  constexpr int kWords = kSigTTeamElems * 10;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTeams12 * kWords];
-  __builtin_amdgcn_s_setprio(3);
-  if constexpr (kPad) asm volatile("" ::: "v255", "a0");
-  Team T = make_team12(lds, kWords);
-  uint32_t* F = T.base + kSigTRegBase * 10;
-  const int idx = blockIdx.x * kTeams12 + team12_index();
-  const bool valid = idx < n;
-  const int ci = valid ? idx : n - 1;
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSig12LdsWords];
+  uint32_t* F;
+  int idx, ci;
+  bool valid;
+  Team T = sig12_team<kPad>(lds, n, F, idx, valid, ci);
   XStream S = x_stream();
   sig12_load_f(T, F, fe, ci);  // the registers the programs read, f into slot F
   t12_conj(T, S_D, S_F);
@@ -370,12 +380,7 @@ __global__ __launch_bounds__(64, kPad ? 1 : 2) void k_sig12_fe(int n, Gt* fe, Gt
   o.d.x = h.v[6];
   o.d.y = h.v[7];
   t12_inv_norm_finish(T, S_B, o, ninv[ci]);
-  // parking as k_verify_sig12
-  SigFE<SigProgs12>::fe_t_rest(T, S, [=](int k) -> uint32_t* {
-    const int i = blockIdx.x * kTeams12 + team12_index();
-    if (k == 0) return (i < n ? fe + i : park + n + 1 + (i - n))->w;
-    return (i < n ? park + i : park + n + 1 + kTeams12 + (i - n))->w;
-  });
+  SigFE<SigProgs12>::fe_t_rest(T, S, Sig12Park{fe, park, n});
   team_sync();
   Fp v;
   ld_fp_a8(v, slot(T, S_F) + T.e * 10);
@@ -386,80 +391,68 @@ __global__ __launch_bounds__(64, kPad ? 1 : 2) void k_sig12_fe(int n, Gt* fe, Gt
   }
 }
 
-bool sig12_for(bool pad, size_t n) {
-  static const int mode = [] {
-    const char* e = getenv("HG_SIG12");
-    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-  }();
-  return n <= (size_t)kSig12MaxN && (mode == 1 || (mode == -1 && !pad));
-}
+// One workspace layout for both callers: [the evaluated lines] | the parking
+// records | [the signatures' scalars] | the split form's hand-over records |
+// norms | inverses, each 256-byte aligned. lines: the bracketed members of a
+// pairing from signatures (launch_sig12); config 2's final exponentiation of
+// given Miller values (launch_fe12) has neither.
+struct Sig12Layout {
+  size_t park, scalars, hand, norm, ninv, bytes;
+  Sig12Layout(int n, bool lines) {
+    auto align256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    park = lines ? align256((size_t)n * kNumLines * 4 * sizeof(Fp)) : 0;
+    scalars = park + align256((size_t)(n + 1 + 2 * kTeams12) * sizeof(Gt));
+    hand = scalars + (lines ? align256((size_t)n * 2 * sizeof(Fp)) : 0);
+    norm = hand + align256((size_t)n * sizeof(SigHand));
+    ninv = norm + align256((size_t)n * sizeof(Fp));
+    bytes = ninv + (size_t)n * sizeof(Fp);
+  }
+};
+size_t sig12_lines_bytes(int n) { return Sig12Layout(n, true).bytes; }
+size_t fe12_ws_bytes(int n) { return Sig12Layout(n, false).bytes; }
 
-// the split form (k_sig12_miller, k_sig12_ninv, k_sig12_fe) for unpadded
-// launches unless HG_SIG12_SPLIT=0
-static bool sig12_split() {
-  static const bool on = [] {
-    const char* e = getenv("HG_SIG12_SPLIT");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-
-// the evaluated lines, then (each 256-byte aligned) the parking records, the
-// signatures' scalars, and the split form's hand-over records and norms
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t sig12_park_offset(int n) { return align256((size_t)n * kNumLines * 4 * sizeof(Fp)); }
-static size_t sig12_scalar_offset(int n) {
-  return sig12_park_offset(n) + align256((size_t)(n + 1 + 2 * kTeams12) * sizeof(Gt));
-}
-static size_t sig12_hand_offset(int n) { return sig12_scalar_offset(n) + align256((size_t)n * 2 * sizeof(Fp)); }
-static size_t sig12_norm_offset(int n) { return sig12_hand_offset(n) + align256((size_t)n * sizeof(SigHand)); }
-static size_t sig12_ninv_offset(int n) { return sig12_norm_offset(n) + align256((size_t)n * sizeof(Fp)); }
-size_t sig12_lines_bytes(int n) { return sig12_ninv_offset(n) + (size_t)n * sizeof(Fp); }
-
-// The final exponentiation of n Miller values already in fe (config 2's
-// k_verify_ml), in place: k_sig12_norm, k_sig12_ninv, k_sig12_fe. ws:
-// fe12_ws_bytes(n) bytes (parking records, hand-over terms, norms, inverses).
-static size_t fe12_hand_offset(int n) { return align256((size_t)(n + 1 + 2 * kTeams12) * sizeof(Gt)); }
-static size_t fe12_norm_offset(int n) { return fe12_hand_offset(n) + align256((size_t)n * sizeof(SigHand)); }
-static size_t fe12_ninv_offset(int n) { return fe12_norm_offset(n) + align256((size_t)n * sizeof(Fp)); }
-size_t fe12_ws_bytes(int n) { return fe12_ninv_offset(n) + (size_t)n * sizeof(Fp); }
-void launch_fe12(Gt* fe, int n, uint8_t* ws, hipStream_t s) {
-  if (n <= 0 || n > kSig12MaxN) return;
-  Gt* park = (Gt*)ws;
-  SigHand* hand = (SigHand*)(ws + fe12_hand_offset(n));
-  Fp* nrm = (Fp*)(ws + fe12_norm_offset(n));
-  Fp* ninv = (Fp*)(ws + fe12_ninv_offset(n));
+// The split chain on workspace `base` laid out by L: the first kernel is
+// k_sig12_miller from the evaluated lines ev, or (ev == nullptr) k_sig12_norm
+// of the Miller values already in fe; then the batched inversion and the rest
+// of the final exponentiation, in place.
+static void launch_split_chain(const Fp* ev, int n, Gt* fe, uint8_t* base, const Sig12Layout& L, hipStream_t s) {
+  Gt* park = (Gt*)(base + L.park);
+  SigHand* hand = (SigHand*)(base + L.hand);
+  Fp* nrm = (Fp*)(base + L.norm);
+  Fp* ninv = (Fp*)(base + L.ninv);
   const int blocks = (n + kTeams12 - 1) / kTeams12;
-  k_sig12_norm<<<blocks, 64, 0, s>>>(n, fe, hand, nrm);
+  if (ev) k_sig12_miller<false><<<blocks, 64, 0, s>>>(ev, n, fe, hand, nrm);
+  else k_sig12_norm<<<blocks, 64, 0, s>>>(n, fe, hand, nrm);
   k_sig12_ninv<<<(n + kInvBlock - 1) / kInvBlock, kInvBlock, 0, s>>>(nrm, n, ninv);
   k_sig12_fe<false><<<blocks, 64, 0, s>>>(n, fe, park, hand, ninv);
 }
 
-void launch_sig_pairing12(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Fp* ev, Gt* fe,
-                          hipStream_t s, bool pad) {
-  // k_sig_lines indexes 4 n threads in int (callers bound n by kSig12MaxN)
-  if (n <= 0 || n > kSig12MaxN) return;
-  uint8_t* base = (uint8_t*)ev;
-  Gt* park = (Gt*)(base + sig12_park_offset(n));
-  Fp* sc = (Fp*)(base + sig12_scalar_offset(n));
+// The launchers below refuse (false, nothing launched) a batch above
+// kSig12MaxN: k_sig_lines indexes 4 n threads in int. sig_form() and
+// verify_split_for() (bn256_sigform.h) never choose these forms there; a
+// caller that got here anyway must not leave its codes at HG_OK.
+bool launch_fe12(Gt* fe, int n, uint8_t* ws, hipStream_t s) {
+  if (n > kSig12MaxN) return false;
+  if (n > 0) launch_split_chain(nullptr, n, fe, ws, Sig12Layout(n, false), s);
+  return true;
+}
+
+// launch_sig_form's T12Pad (pad) and T12 (split: sig_form_split) bodies
+bool launch_sig12(bool pad, bool split, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws,
+                  Gt* fe, hipStream_t s) {
+  if (n > kSig12MaxN) return false;
+  if (n <= 0) return true;
+  const Sig12Layout L(n, true);
+  Fp* ev = (Fp*)ws;
+  Fp* sc = (Fp*)(ws + L.scalars);
   k_sig_scalars<<<(n + kLineBlock - 1) / kLineBlock, kLineBlock, 0, s>>>(sigs, flavor, n, sc);
   k_sig_lines<<<dim3((4 * n + kLineBlock - 1) / kLineBlock, kNumLines), kLineBlock, 0, s>>>(sc, n, tab, ev);
   const int blocks = (n + kTeams12 - 1) / kTeams12;
-  // the split form for unpadded launches only (batches in flight share the
-  // SIMDs, so the inversion kernel's latency hides behind other batches'
-  // waves); a padded launch runs alone at one wave per SIMD, where the single
-  // kernel is faster (0.947 vs 0.964 ms per 4096, profiles/r06b_sig12_split_ab.json)
-  if (sig12_split() && !pad) {
-    SigHand* hand = (SigHand*)(base + sig12_hand_offset(n));
-    Fp* nrm = (Fp*)(base + sig12_norm_offset(n));
-    Fp* ninv = (Fp*)(base + sig12_ninv_offset(n));
-    k_sig12_miller<false><<<blocks, 64, 0, s>>>(ev, n, fe, hand, nrm);
-    k_sig12_ninv<<<(n + kInvBlock - 1) / kInvBlock, kInvBlock, 0, s>>>(nrm, n, ninv);
-    k_sig12_fe<false><<<blocks, 64, 0, s>>>(n, fe, park, hand, ninv);
-    return;
-  }
-  if (pad) k_verify_sig12<true><<<blocks, 64, 0, s>>>(ev, n, fe, park);
+  Gt* park = (Gt*)(ws + L.park);
+  if (split) launch_split_chain(ev, n, fe, ws, L, s);
+  else if (pad) k_verify_sig12<true><<<blocks, 64, 0, s>>>(ev, n, fe, park);
   else k_verify_sig12<false><<<blocks, 64, 0, s>>>(ev, n, fe, park);
+  return true;
 }
 
 }  // namespace hg

@@ -7,7 +7,8 @@
 
 namespace hg {
 
-void launch_sig_pairing_w2(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s) {
+// launch_sig_form's W2 body (bn256_gt.hip)
+void launch_sig_w2(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s) {
   if (n > 0) k_verify_sig_split<2><<<(n + 3) / 4, 64 * 2, 0, s>>>(sigs, flavor, n, tab, fe);
 }
 

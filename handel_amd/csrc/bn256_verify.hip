@@ -2,7 +2,6 @@
 // e(H, pk) * e(-sig, G2Base) == 1 (PublicKey.VerifySignature, bn256/go/bn256.go:82-94),
 // one 16-lane team per check, TEAMS teams per single-wave workgroup.
 #define HG_DIAG_TU 1
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 
 #include "bn256_gt.h"
@@ -119,28 +118,25 @@ __global__ __launch_bounds__(256) void k_fe_verdicts(const Gt* fe, int n, int32_
   codes[c] = diff == 0 ? HG_OK : HG_ERR_SIG_INVALID;
 }
 
-size_t verify_split_ws_bytes(int n) { return ((size_t)n * sizeof(Gt) + 255) / 256 * 256 + fe12_ws_bytes(n); }
+// the Miller values, then (256-byte aligned) launch_fe12's workspace
+static size_t fe_bytes(int n) { return ((size_t)n * sizeof(Gt) + 255) / 256 * 256; }
+size_t verify_split_ws_bytes(int n) { return fe_bytes(n) + fe12_ws_bytes(n); }
 
-void launch_verify_split(const CheckIn* in, int n, const LineCoef* tab, const PointG1* h, int32_t* codes,
+// false (nothing launched, the codes untouched) above kSig12MaxN, which
+// verify_split_for (bn256_sigform.h) never sends here
+bool launch_verify_split(const CheckIn* in, int n, const LineCoef* tab, const PointG1* h, int32_t* codes,
                          uint8_t* ws, hipStream_t s) {
-  if (n <= 0 || n > kSig12MaxN) return;
+  if (n > kSig12MaxN) return false;
+  if (n <= 0) return true;
   Gt* fe = (Gt*)ws;
   k_verify_ml<4><<<nblk(n, 4), 64, 0, s>>>(in, n, tab, h, fe);
-  launch_fe12(fe, n, ws + ((size_t)n * sizeof(Gt) + 255) / 256 * 256, s);
+  launch_fe12(fe, n, ws + fe_bytes(n), s);
   k_fe_verdicts<<<nblk(n, 256), 256, 0, s>>>(fe, n, codes);
+  return true;
 }
 
 void launch_verify(const CheckIn* in, int n, const LineCoef* tab, const PointG1* h, int32_t* codes, hipStream_t s) {
-  // HG_TEAMS_PER_BLOCK (diagnostic): fewer checks per wave -> more waves per SIMD
-  static const int tpb = [] {
-    const char* e = getenv("HG_TEAMS_PER_BLOCK");
-    int v = e ? atoi(e) : kTeamsPerBlock;
-    return (v >= 1 && v <= kTeamsPerBlock) ? v : kTeamsPerBlock;
-  }();
-  if (n <= 0) return;
-  if (tpb == 4) k_verify<4><<<nblk(n, 4), 64, 0, s>>>(in, n, tab, h, codes);
-  else if (tpb == 2) k_verify<2><<<nblk(n, 2), 32, 0, s>>>(in, n, tab, h, codes);
-  else k_verify<1><<<n, 16, 0, s>>>(in, n, tab, h, codes);
+  if (n > 0) k_verify<4><<<nblk(n, 4), 64, 0, s>>>(in, n, tab, h, codes);
 }
 int diag_read(uint64_t* out, size_t n) {
 #ifdef HG_DIAG

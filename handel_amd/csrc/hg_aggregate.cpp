@@ -221,21 +221,44 @@ struct FoldCaps {
 static FoldCaps fold_caps_worst(const hg_ctx* c, size_t n) {
   FoldCaps one;
   one.add(c->nreg);
-  FoldCaps all;
-  all.terms = one.terms * n;
-  all.chunks = one.chunks * n;
-  return all;
+  return FoldCaps{one.terms * n, one.chunks * n};
 }
+// a lane's largest batch: n requests over max_words bitset words
+static FoldCaps fold_caps_lane(size_t n, size_t max_words) {
+  const size_t terms = 8 * (max_words + n) + n;  // sum of fold_terms_bound over the batch
+  return FoldCaps{terms, terms / (size_t)gt_chunk() + n};
+}
+
+// The parts of a workspace set a batch of n requests needs, sized in one place
+// for a submission and for a lane (every part it may ever use at its largest
+// batch: a buffer that grew later would be freed and reallocated between
+// batches, and freeing device memory waits for the whole device). Verify: the
+// decoded signatures and their codes; Level: level codes computed here; G2Fold,
+// GtFold (caps): the folds'; AggOut: the aggregate keys; Pairing: the FE values
+// and launch_sig_form's sig_bytes; Side: the side stream and its events.
+enum : unsigned { kWsVerify = 1, kWsLevel = 2, kWsG2Fold = 4, kWsAggOut = 8, kWsGtFold = 16, kWsPairing = 32, kWsSide = 64 };
+static hipError_t ws_ensure(Ws& ws, size_t n, unsigned parts, const FoldCaps& caps = {}, size_t sig_bytes = 0) {
+  hipError_t e = hipSuccess;
+  auto grow = [&e](auto& buf, size_t count) {
+    if (e == hipSuccess) e = buf.ensure(count);
+  };
+  if (parts & kWsVerify) grow(ws.pts1, n), grow(ws.codes_b, n);
+  if (parts & kWsLevel) grow(ws.codes_c, n);
+  if (parts & kWsG2Fold) grow(ws.checks, n), grow(ws.order, n), grow(ws.agg_ws, n * agg_partial_bytes() + agg_fixed_bytes());
+  if (parts & kWsAggOut) grow(ws.pts2, n);
+  if (parts & kWsGtFold) {
+    grow(ws.gt_plan, n), grow(ws.gt_hdr, 1), grow(ws.gt_terms, caps.terms), grow(ws.gt_ord, caps.chunks);
+    grow(ws.gt_multi, 2 * n), grow(ws.gt_partial, caps.chunks), grow(ws.gt_y, n);
+  }
+  if (parts & kWsPairing) grow(ws.gt_fe, n), grow(ws.sig_lines, sig_bytes);
+  if ((parts & kWsSide) && e == hipSuccess) e = ensure_side(ws);
+  return e;
+}
+
 static int ensure_gt_fold(hg_ctx* c, Ws& ws, size_t n, const FoldCaps& caps, GtWork& w) {
   static const int grid = env_int("HG_GT_GRID", 4096, 64, 65536);
   if (caps.chunks > (size_t)INT32_MAX || caps.terms > (size_t)INT32_MAX) return kNoMem;
-  HG_GT_ALLOC(c, ws.gt_plan.ensure(n));
-  HG_GT_ALLOC(c, ws.gt_hdr.ensure(1));
-  HG_GT_ALLOC(c, ws.gt_terms.ensure(caps.terms));
-  HG_GT_ALLOC(c, ws.gt_ord.ensure(caps.chunks));
-  HG_GT_ALLOC(c, ws.gt_multi.ensure(2 * n));
-  HG_GT_ALLOC(c, ws.gt_partial.ensure(caps.chunks));
-  HG_GT_ALLOC(c, ws.gt_y.ensure(n));
+  HG_GT_ALLOC(c, ws_ensure(ws, n, kWsGtFold, caps));
   w.plan = ws.gt_plan.p;
   w.hdr = ws.gt_hdr.p;
   w.terms = ws.gt_terms.p;
@@ -290,141 +313,153 @@ __global__ void k_level_codes(const hg_request* r, int n, uint32_t nreg, int32_t
   out[i] = ok ? HG_OK : HG_ERR_LEVEL;
 }
 
-// The Combine fold and (verify) the pairing check of n requests, device
-// pointers, on stream s; d_lvl holds the level codes and is updated in place
-// (nullptr: computed here when the flow needs them). caps: the fold's list
-// capacities (nullptr: bounded by the registry size).
-// d_bits (nullable): the verdict bitset of the codes, written in the same
-// submission (hg_pack_verdicts_device's layout)
-// lane (nullable): a service lane's submission — its own workspaces, outside
-// the context's submission chain, never building tables.
-static int aggregate_device_locked(hg_ctx* c, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
-                                   const uint8_t* d_sigs, int32_t* d_codes, uint8_t* d_agg, int32_t* d_lvl,
-                                   bool verify, hipStream_t s, const FoldCaps* caps = nullptr,
-                                   uint8_t* d_bits = nullptr, hg_lane* lane = nullptr) {
+// One batch on the device: n requests, their bitset words and signatures in;
+// codes (and, nullable, agg: the aggregate keys' marshals; bits: the verdict
+// bitset of the codes, hg_pack_verdicts_device's layout) out. lvl (nullable):
+// the level codes, updated in place; computed here when the flow needs them.
+// caps (nullable): the fold's list capacities; else bounded by the registry.
+struct AggBatch {
+  const hg_request* reqs;
+  size_t n;
+  const uint64_t* words;
+  const uint8_t* sigs;
+  int32_t* codes;
+  uint8_t* agg = nullptr;
+  int32_t* lvl = nullptr;
+  uint8_t* bits = nullptr;
+  const FoldCaps* caps = nullptr;
+};
+
+static void gt_prologue(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
+  launch_agg_prologue(b.reqs, (int)b.n, (uint32_t)c->nreg, b.sigs, c->flavor, ws.pts1.p, b.codes, (int*)gw.hdr,
+                      (int)(sizeof(GtHdr) / sizeof(int)), s);
+}
+static void gt_fold(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, int32_t* codes, bool zero_hdr,
+                    hipStream_t s) {
+  launch_gt_fold(b.reqs, (int)b.n, b.words, codes, (int)c->nreg, c->block_levels,
+                 gw.win_bits == 16 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, zero_hdr,
+                 s);
+}
+
+// GT path, verdicts only, the fold beside the pairing:
+// s:    pairing (decodes its signatures) ............ -> wait -> compare
+// side: wait -> prologue (codes, counters), plan, chunks, combine -> join
+static int flow_gt_beside(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, const GtWork& gw, hipStream_t s) {
+  const int n = (int)b.n;
+  HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
+  PhaseTimer t(c, HG_PHASE_VERIFY, s);
+  const bool ran = launch_sig_form(form, b.sigs, c->flavor, n, c->d_lines.p, ws.sig_lines.p, ws.gt_fe.p, s);
+  t.stop();
+  if (!ran) {
+    c->err = "aggregate batch too large for its pairing form";
+    return HG_ERR_ARG;
+  }
+  HG_CHECK(c, hipStreamWaitEvent(ws.side, ws.ev_fork, 0));
+  gt_prologue(c, b, ws, gw, ws.side);
+  PhaseTimer fold(c, HG_PHASE_AGGREGATE, ws.side);
+  gt_fold(c, b, ws, gw, b.codes, false, ws.side);
+  fold.stop();
+  HG_CHECK(c, hipEventRecord(ws.ev_join, ws.side));
+  HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
+  if (b.bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
+  else launch_gt_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, s);
+  return HG_OK;
+}
+
+// GT path, verdicts only, in sequence: level check, signature decode and the
+// fold's counters in one launch, then the fold and k_verify_sig on the codes
+static int flow_gt_sequence(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
+  const int n = (int)b.n;
+  gt_prologue(c, b, ws, gw, s);
+  PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
+  gt_fold(c, b, ws, gw, b.codes, false, s);
+  fold.stop();
+  PhaseTimer t(c, HG_PHASE_VERIFY, s);
+  launch_verify_sig(ws.pts1.p, n, c->d_lines.p, ws.gt_y.p, b.codes, s);
+  t.stop();
+  if (b.bits) launch_pack_verdicts(b.codes, n, b.bits, s);
+  return HG_OK;
+}
+
+// The G2 fold (g2_fold: no tables, or the caller wants the aggregate keys'
+// marshals), the GT fold beside it when use_gt, and (verify) the check:
+// k_verify_sig against the GT fold's values, or config 2 on the G2 fold's
+static int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, bool use_gt, bool g2_fold,
+                            const GtWork& gw, hipStream_t s) {
+  const int n = (int)b.n;
+  int32_t* d_lvl = b.lvl;
+  if (!d_lvl) {
+    d_lvl = ws.codes_c.p;
+    k_level_codes<<<nb(b.n), 256, 0, s>>>(b.reqs, n, (uint32_t)c->nreg, d_lvl);
+  }
+  PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
+  if (g2_fold)
+    launch_aggregate(c->wsum.p, (int)c->nreg, c->blocks.p, c->block_base.data(), c->block_levels, b.reqs, n, b.words,
+                     ws.order.p, ws.agg_ws.p, ws.checks.p, d_lvl, s);
+  if (use_gt) gt_fold(c, b, ws, gw, d_lvl, true, s);
+  fold.stop();
+  if (b.agg) {
+    launch_extract_pk(ws.checks.p, n, ws.pts2.p, s);
+    launch_encode_g2(ws.pts2.p, n, b.agg, s);
+  }
+  if (verify) {
+    launch_decode_g1(b.sigs, n, c->flavor, ws.pts1.p, ws.codes_b.p, s);
+    k_agg_codes<<<nb(b.n), 256, 0, s>>>(ws.codes_b.p, d_lvl, c->cur.hash_eof ? 1 : 0, n, b.codes);
+    if (use_gt) {
+      PhaseTimer t(c, HG_PHASE_VERIFY, s);
+      launch_verify_sig(ws.pts1.p, n, c->d_lines.p, ws.gt_y.p, b.codes, s);
+      t.stop();
+    } else if (!c->cur.hash_eof) {
+      launch_sig_into_checks(ws.pts1.p, n, ws.checks.p, s);
+      PhaseTimer t(c, HG_PHASE_VERIFY, s);
+      launch_verify(ws.checks.p, n, c->d_lines.p, c->cur.d_h.p, b.codes, s);
+      t.stop();
+    }
+  }
+  if (b.bits) launch_pack_verdicts(b.codes, n, b.bits, s);
+  return HG_OK;
+}
+
+// The Combine fold and (verify) the pairing check of a batch on stream s,
+// with the workspaces ws and the pairing policy pol: the context's own, or a
+// service lane's (is_lane: outside the context's submission chain, and never
+// building tables).
+static int aggregate_device_locked(hg_ctx* c, const AggBatch& b, bool verify, hipStream_t s, Ws& ws,
+                                   const SigPolicy& pol, bool is_lane) {
   if (verify && !c->cur.has_msg) {
     c->err = "hg_set_message was not called";
     return HG_ERR_ARG;
   }
-  Ws& ws = lane ? lane->ws : c->ws;
+  const size_t n = b.n;
   Submission sub(c, s);
-  if (!lane) HG_CHECK(c, sub.start());
+  if (!is_lane) HG_CHECK(c, sub.start());
   // GT path: the verdict needs no aggregate key in G2; the G2 fold still runs
   // when the caller wants the aggregate keys' marshals
   int level = verify ? gt_submission_level(c, n) : 0;
   GtWork gw{};
   if (level > 0) {
-    const FoldCaps fc = caps ? *caps : fold_caps_worst(c, n);
-    int rc = gt_acquire(c, ws, s, n, fc, level, gw, lane == nullptr);
+    int rc = gt_acquire(c, ws, s, n, b.caps ? *b.caps : fold_caps_worst(c, n), level, gw, !is_lane);
     if (rc) return rc;
-  }
-  const bool use_gt = level > 0;
-  const bool g2_fold = !use_gt || d_agg;
-  if (g2_fold) {
-    HG_CHECK(c, ws.checks.ensure(n));
-    HG_CHECK(c, ws.order.ensure(n));
-    HG_CHECK(c, ws.agg_ws.ensure(n * agg_partial_bytes() + agg_fixed_bytes()));
-  }
-  if (d_agg) HG_CHECK(c, ws.pts2.ensure(n));
-  if (!d_lvl) HG_CHECK(c, ws.codes_c.ensure(n));
-  if (verify) {
-    HG_CHECK(c, ws.pts1.ensure(n));
-    HG_CHECK(c, ws.codes_b.ensure(n));
   }
   gw.win_bits = level == 2 ? 16 : 8;
+  const bool use_gt = level > 0;
+  const bool g2_fold = !use_gt || b.agg;
+  const bool beside = use_gt && !g2_fold && pol.overlap;
+  // the pairing's form: chosen once, it sizes the workspace and is what runs
+  const SigForm form = sig_form(sig_env(), pol, n);
+  const unsigned parts = (g2_fold ? kWsG2Fold : 0) | (b.agg ? kWsAggOut : 0) | (b.lvl ? 0 : kWsLevel) |
+                         (verify ? kWsVerify : 0) | (beside ? kWsPairing | kWsSide : 0);
+  HG_CHECK(c, ws_ensure(ws, n, parts, {}, sig_form_ws_bytes(form, (int)n)));
   PhaseTimer all(c, HG_PHASE_SUBMIT, s);
-  if (use_gt && !g2_fold) {
-    // GT path, verdicts only: level check, signature decode and the fold's
-    // counters in one launch, then the fold and the check on d_codes
-    const bool overlap = lane ? lane->overlap : c->overlap;
-    if (overlap) {
-      HG_CHECK(c, ensure_side(ws));
-      HG_CHECK(c, ws.gt_fe.ensure(n));
-      if (sig12_for(lane ? lane->pad : true, n)) HG_CHECK(c, ws.sig_lines.ensure(sig12_lines_bytes((int)n)));
-    }
-    if (overlap) {
-      // s:    pairing (decodes its signatures) ............ -> wait -> compare
-      // side: wait -> prologue (codes, counters), plan, chunks, combine -> join
-      HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
-      PhaseTimer t(c, HG_PHASE_VERIFY, s);
-      if (sig12_for(lane ? lane->pad : true, n))
-        launch_sig_pairing12(d_sigs, c->flavor, (int)n, c->d_lines.p, (Fp*)ws.sig_lines.p, ws.gt_fe.p, s,
-                             lane ? lane->pad : true);
-      else
-        // the two-wave latency form for the context's own submissions (one
-        // batch at a time); lanes keep batches in flight, where twice the
-        // waves per check costs throughput (HG_SIG_W2_LANE_MAX: A/B)
-        launch_sig_pairing(d_sigs, c->flavor, (int)n, c->d_lines.p, ws.gt_fe.p, s, lane ? lane->pad : true,
-                           lane ? lane->w2_max : kSigW2MaxN);
-      t.stop();
-      HG_CHECK(c, hipStreamWaitEvent(ws.side, ws.ev_fork, 0));
-      launch_agg_prologue(d_reqs, (int)n, (uint32_t)c->nreg, d_sigs, c->flavor, ws.pts1.p, d_codes, (int*)gw.hdr,
-                          (int)(sizeof(GtHdr) / sizeof(int)), ws.side);
-      PhaseTimer fold(c, HG_PHASE_AGGREGATE, ws.side);
-      launch_gt_fold(d_reqs, (int)n, d_words, d_codes, (int)c->nreg, c->block_levels,
-                     level == 2 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, false, ws.side);
-      fold.stop();
-      HG_CHECK(c, hipEventRecord(ws.ev_join, ws.side));
-      HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
-      if (d_bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, (int)n, d_codes, d_bits, s);
-      else launch_gt_compare(ws.gt_fe.p, ws.gt_y.p, (int)n, d_codes, s);
-      all.stop();
-      int rc = check_launch(c);
-      if (rc) return rc;
-      if (!lane) HG_CHECK(c, sub.finish());
-      return HG_OK;
-    }
-    launch_agg_prologue(d_reqs, (int)n, (uint32_t)c->nreg, d_sigs, c->flavor, ws.pts1.p, d_codes, (int*)gw.hdr,
-                        (int)(sizeof(GtHdr) / sizeof(int)), s);
-    PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
-    launch_gt_fold(d_reqs, (int)n, d_words, d_codes, (int)c->nreg, c->block_levels,
-                   level == 2 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, false, s);
-    fold.stop();
-    PhaseTimer t(c, HG_PHASE_VERIFY, s);
-    launch_verify_sig(ws.pts1.p, (int)n, c->d_lines.p, ws.gt_y.p, d_codes, s);
-    t.stop();
-    if (d_bits) launch_pack_verdicts(d_codes, (int)n, d_bits, s);
-    all.stop();
-    int rc = check_launch(c);
-    if (rc) return rc;
-    if (!lane) HG_CHECK(c, sub.finish());
-    return HG_OK;
-  }
-  if (!d_lvl) {
-    d_lvl = ws.codes_c.p;
-    k_level_codes<<<nb(n), 256, 0, s>>>(d_reqs, (int)n, (uint32_t)c->nreg, d_lvl);
-  }
-  PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
-  if (g2_fold)
-    launch_aggregate(c->wsum.p, (int)c->nreg, c->blocks.p, c->block_base.data(), c->block_levels, d_reqs, (int)n,
-                     d_words, ws.order.p, ws.agg_ws.p, ws.checks.p, d_lvl, s);
-  if (use_gt)
-    launch_gt_fold(d_reqs, (int)n, d_words, d_lvl, (int)c->nreg, c->block_levels,
-                   level == 2 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, true, s);
-  fold.stop();
-  if (d_agg) {
-    launch_extract_pk(ws.checks.p, (int)n, ws.pts2.p, s);
-    launch_encode_g2(ws.pts2.p, (int)n, d_agg, s);
-  }
-  if (verify) {
-    launch_decode_g1(d_sigs, (int)n, c->flavor, ws.pts1.p, ws.codes_b.p, s);
-    k_agg_codes<<<nb(n), 256, 0, s>>>(ws.codes_b.p, d_lvl, c->cur.hash_eof ? 1 : 0, (int)n, d_codes);
-    if (use_gt) {
-      PhaseTimer t(c, HG_PHASE_VERIFY, s);
-      launch_verify_sig(ws.pts1.p, (int)n, c->d_lines.p, ws.gt_y.p, d_codes, s);
-      t.stop();
-    } else if (!c->cur.hash_eof) {
-      launch_sig_into_checks(ws.pts1.p, (int)n, ws.checks.p, s);
-      PhaseTimer t(c, HG_PHASE_VERIFY, s);
-      launch_verify(ws.checks.p, (int)n, c->d_lines.p, c->cur.d_h.p, d_codes, s);
-      t.stop();
-    }
-  }
-  if (d_bits) launch_pack_verdicts(d_codes, (int)n, d_bits, s);
-  all.stop();
-  int rc = check_launch(c);
+  int rc;
+  if (beside) rc = flow_gt_beside(c, b, ws, form, gw, s);
+  else if (use_gt && !g2_fold) rc = flow_gt_sequence(c, b, ws, gw, s);
+  else rc = flow_g2_or_mixed(c, b, ws, verify, use_gt, g2_fold, gw, s);
   if (rc) return rc;
-  if (!lane) HG_CHECK(c, sub.finish());
+  all.stop();
+  rc = check_launch(c);
+  if (rc) return rc;
+  if (!is_lane) HG_CHECK(c, sub.finish());
   return HG_OK;
 }
 
@@ -458,8 +493,9 @@ static int aggregate_host_locked(hg_ctx* c, const hg_request* reqs, size_t n, co
   if (nwords) HG_CHECK(c, hipMemcpyAsync(c->words.p, words, nwords * 8, hipMemcpyHostToDevice, c->stream));
   HG_CHECK(c, hipMemcpyAsync(c->ws.codes_c.p, lvl.data(), n * 4, hipMemcpyHostToDevice, c->stream));
   if (verify) HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, c->stream));
-  int rc = aggregate_device_locked(c, c->reqs.p, n, c->words.p, verify ? c->bytes_b.p : nullptr, c->codes_a.p, d_agg,
-                                   c->ws.codes_c.p, verify, c->stream, &caps);
+  const AggBatch b{c->reqs.p, n, c->words.p, verify ? c->bytes_b.p : nullptr, c->codes_a.p, d_agg, c->ws.codes_c.p,
+                   nullptr, &caps};
+  int rc = aggregate_device_locked(c, b, verify, c->stream, c->ws, c->pol, false);
   if (rc) return rc;
   if (agg_out) HG_CHECK(c, hipMemcpyAsync(agg_out, d_agg, n * 128, hipMemcpyDeviceToHost, c->stream));
   HG_CHECK(c, hipMemcpyAsync(codes, verify ? c->codes_a.p : c->ws.codes_c.p, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -524,7 +560,7 @@ int hg_set_aggregate_level(hg_ctx* c, int level) {
 int hg_set_fold_overlap(hg_ctx* c, int on) {
   if (!c) return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  c->overlap = on != 0;
+  c->pol.overlap = on != 0;
   return HG_OK;
 }
 
@@ -569,7 +605,8 @@ int hg_verify_aggregate_device(hg_ctx* c, const hg_request* d_reqs, size_t n, co
   std::lock_guard<std::mutex> g(c->mu);
   HG_CHECK(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  return aggregate_device_locked(c, d_reqs, n, d_words, d_sigs, d_codes, d_agg_pk_out, nullptr, true, s);
+  return aggregate_device_locked(c, AggBatch{d_reqs, n, d_words, d_sigs, d_codes, d_agg_pk_out}, true, s, c->ws, c->pol,
+                                 false);
 }
 
 int hg_verify_aggregate_device_bits(hg_ctx* c, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
@@ -579,7 +616,8 @@ int hg_verify_aggregate_device_bits(hg_ctx* c, const hg_request* d_reqs, size_t 
   std::lock_guard<std::mutex> g(c->mu);
   HG_CHECK(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  return aggregate_device_locked(c, d_reqs, n, d_words, d_sigs, d_codes, nullptr, nullptr, true, s, nullptr, d_bits);
+  return aggregate_device_locked(c, AggBatch{d_reqs, n, d_words, d_sigs, d_codes, nullptr, nullptr, d_bits}, true, s,
+                                 c->ws, c->pol, false);
 }
 
 int hg_verify_aggregate(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
@@ -640,7 +678,7 @@ int hg_lane_create(hg_ctx* c, size_t max_batch, size_t max_words, int overlap, h
   HG_CHECK(c, hipSetDevice(c->device));
   hg_lane* l = new hg_lane();
   l->c = c;
-  l->overlap = overlap != 0;
+  l->pol.overlap = overlap != 0;
   l->max_batch = max_batch;
   l->max_words = max_words;
   // staging: requests | signatures | words, each 256-byte aligned
@@ -653,29 +691,12 @@ int hg_lane_create(hg_ctx* c, size_t max_batch, size_t max_words, int overlap, h
   if (e == hipSuccess) e = l->h_codes.alloc(max_batch);
   if (e == hipSuccess) e = l->d_in.ensure(bytes);
   if (e == hipSuccess) e = l->d_codes.ensure(max_batch);
-  // every workspace at its largest now (max_batch requests over max_words
-  // bitset words): a buffer that grew later would be freed and reallocated
-  // between batches, and freeing device memory waits for the whole device
-  const size_t n = max_batch;
-  const size_t terms = 8 * (max_words + n) + n;  // sum of fold_terms_bound over the batch
-  const size_t chunks = terms / (size_t)gt_chunk() + n;
-  Ws& w = l->ws;
-  if (e == hipSuccess) e = w.pts1.ensure(n);
-  if (e == hipSuccess) e = w.codes_b.ensure(n);
-  if (e == hipSuccess) e = w.codes_c.ensure(n);
-  if (e == hipSuccess) e = w.checks.ensure(n);
-  if (e == hipSuccess) e = w.order.ensure(n);
-  if (e == hipSuccess) e = w.agg_ws.ensure(n * agg_partial_bytes() + agg_fixed_bytes());
-  if (e == hipSuccess) e = w.gt_plan.ensure(n);
-  if (e == hipSuccess) e = w.gt_hdr.ensure(1);
-  if (e == hipSuccess) e = w.gt_terms.ensure(terms);
-  if (e == hipSuccess) e = w.gt_ord.ensure(chunks);
-  if (e == hipSuccess) e = w.gt_multi.ensure(2 * n);
-  if (e == hipSuccess) e = w.gt_partial.ensure(chunks);
-  if (e == hipSuccess) e = w.gt_y.ensure(n);
-  if (e == hipSuccess) e = w.gt_fe.ensure(n);
-  if (e == hipSuccess && sig12_for(true, n)) e = w.sig_lines.ensure(sig12_lines_bytes((int)n));
-  if (e == hipSuccess && l->overlap) e = ensure_side(w);
+  // every workspace at its largest now (ws_ensure)
+  if (e == hipSuccess)
+    e = ws_ensure(l->ws, max_batch,
+                  kWsVerify | kWsLevel | kWsG2Fold | kWsGtFold | kWsPairing | (l->pol.overlap ? kWsSide : 0),
+                  fold_caps_lane(max_batch, max_words),
+                  sig_form_ws_bytes(sig_form(sig_env(), l->pol, max_batch), (int)max_batch));
   if (e != hipSuccess) {
     c->err = std::string("hg_lane_create: ") + hipGetErrorString(e);
     delete l;
@@ -734,9 +755,9 @@ int hg_lane_submit(hg_lane* l) {
   if (c->last_ev) HG_CHECK(c, hipStreamWaitEvent(l->s, c->last_ev, 0));
   uint8_t* d = l->d_in.p;
   HG_CHECK(c, hipMemcpyAsync(d, l->h_in.get(), l->in_bytes, hipMemcpyHostToDevice, l->s));
-  int rc = aggregate_device_locked(c, reinterpret_cast<const hg_request*>(d), n,
-                                   reinterpret_cast<const uint64_t*>(d + l->off_words), d + l->off_sigs,
-                                   l->d_codes.p, nullptr, nullptr, true, l->s, &caps, nullptr, l);
+  const AggBatch b{reinterpret_cast<const hg_request*>(d), n, reinterpret_cast<const uint64_t*>(d + l->off_words),
+                   d + l->off_sigs, l->d_codes.p, nullptr, nullptr, nullptr, &caps};
+  int rc = aggregate_device_locked(c, b, true, l->s, l->ws, l->pol, true);
   if (rc) return rc;
   HG_CHECK(c, hipMemcpyAsync(l->h_codes.get(), l->d_codes.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, l->s));
   HG_CHECK(c, hipEventRecord(l->done, l->s));
@@ -751,22 +772,24 @@ int hg_lane_set_pairing_padding(hg_lane* l, int pad) {
   if (!l) return HG_ERR_ARG;
   hg_ctx* c = l->c;
   std::lock_guard<std::mutex> g(c->mu);
-  // the unpadded lane runs the 12-lane kernel: its evaluated-line workspace
-  // at the lane's largest batch now (never grown between batches)
-  if (sig12_for(pad != 0, l->max_batch)) {
+  // the lane's pairing workspace at its largest batch now (never grown between
+  // batches): the unpadded lane runs the 12-lane form on evaluated lines
+  SigPolicy pol = l->pol;
+  pol.pad = pad != 0;
+  if (const size_t bytes = sig_form_ws_bytes(sig_form(sig_env(), pol, l->max_batch), (int)l->max_batch)) {
     HG_CHECK(c, hipSetDevice(c->device));
     HG_CHECK(c, hipStreamSynchronize(l->s));
     if (l->ws.side) HG_CHECK(c, hipStreamSynchronize(l->ws.side));
-    HG_CHECK(c, l->ws.sig_lines.ensure(sig12_lines_bytes((int)l->max_batch)));
+    HG_CHECK(c, l->ws.sig_lines.ensure(bytes));
   }
-  l->pad = pad != 0;
+  l->pol = pol;
   return HG_OK;
 }
 
 int hg_lane_set_latency_form(hg_lane* l, int max_checks) {
   if (!l || max_checks < 0) return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(l->c->mu);
-  l->w2_max = max_checks < kSigW2MaxN ? max_checks : kSigW2MaxN;
+  l->pol.w2_max = max_checks < kSigW2MaxN ? max_checks : kSigW2MaxN;
   return HG_OK;
 }
 
@@ -783,8 +806,8 @@ int hg_lane_submit_device(hg_lane* l, const hg_request* d_reqs, size_t n, const 
   HG_CHECK(c, hipStreamWaitEvent(l->s, l->ev_in, 0));
   if (c->last_ev) HG_CHECK(c, hipStreamWaitEvent(l->s, c->last_ev, 0));
   const FoldCaps caps = fold_caps_worst(c, n);  // the device words are not visible to the host
-  int rc = aggregate_device_locked(c, d_reqs, n, d_words, d_sigs, d_codes, nullptr, nullptr, true, l->s, &caps,
-                                   d_bits, l);
+  const AggBatch b{d_reqs, n, d_words, d_sigs, d_codes, nullptr, nullptr, d_bits, &caps};
+  int rc = aggregate_device_locked(c, b, true, l->s, l->ws, l->pol, true);
   if (rc) return rc;
   HG_CHECK(c, hipEventRecord(l->done, l->s));
   l->recorded = true;

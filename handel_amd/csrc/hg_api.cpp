@@ -27,16 +27,17 @@ __global__ void k_fill_codes(int32_t* c, int n, int32_t from, int32_t to) {
 }
 }  // namespace
 
-// config 2's split form (launch_verify_split: the Miller loop on a compact
-// team region, the 12-lane final exponentiation): hg_set_verify_split
-static bool verify_split_for(const hg_ctx* c, size_t n) { return c->verify_split && n <= (size_t)kSig12MaxN; }
-
-static void timed_verify(hg_ctx* c, const CheckIn* in, int n, int32_t* codes, hipStream_t s,
+// config 2, in its split form (launch_verify_split: the Miller loop on a
+// compact team region, the 12-lane final exponentiation) on split_ws where
+// verify_split_for chose it (hg_set_verify_split); false: refused, nothing ran
+static bool timed_verify(hg_ctx* c, const CheckIn* in, int n, int32_t* codes, hipStream_t s,
                          uint8_t* split_ws = nullptr) {
   PhaseTimer t(c, HG_PHASE_VERIFY, s);
-  if (split_ws) launch_verify_split(in, n, c->d_lines.p, c->cur.d_h.p, codes, split_ws, s);
+  bool ok = true;
+  if (split_ws) ok = launch_verify_split(in, n, c->d_lines.p, c->cur.d_h.p, codes, split_ws, s);
   else launch_verify(in, n, c->d_lines.p, c->cur.d_h.p, codes, s);
   t.stop();
+  return ok;
 }
 
 static bool same_msg(const std::vector<uint8_t>& m, const uint8_t* msg, size_t len) {
@@ -91,14 +92,17 @@ static int verify_batch_device_locked(hg_ctx* c, const uint8_t* d_pks, const uin
     return HG_ERR_ARG;
   }
   HG_CHECK(c, c->ws.checks.ensure(n));
-  const bool split = verify_split_for(c, n);
+  const bool split = verify_split_for(c->verify_split, n);
   if (split) HG_CHECK(c, c->ws.sig_lines.ensure(verify_split_ws_bytes((int)n)));
   Submission sub(c, s);
   HG_CHECK(c, sub.start());
   PhaseTimer all(c, HG_PHASE_SUBMIT, s);
   launch_decode_checks(d_pks, d_sigs, (int)n, c->flavor, c->ws.checks.p, d_codes, s);
   if (c->cur.hash_eof) k_fill_codes<<<nb(n), 256, 0, s>>>(d_codes, (int)n, HG_OK, HG_ERR_HASH_EOF);
-  else timed_verify(c, c->ws.checks.p, (int)n, d_codes, s, split ? c->ws.sig_lines.p : nullptr);
+  else if (!timed_verify(c, c->ws.checks.p, (int)n, d_codes, s, split ? c->ws.sig_lines.p : nullptr)) {
+    c->err = "hg_verify_batch: batch too large for the split form";
+    return HG_ERR_ARG;
+  }
   all.stop();
   int rc = check_launch(c);
   if (rc) return rc;
@@ -173,8 +177,8 @@ int hg_create(int device, int flavor, hg_ctx** out) {
   c->device = device;
   c->flavor = flavor;
   c->pinned_level = gt_forced_level();
-  c->overlap = gt_overlap();
-  c->verify_split = env_int("HG_VERIFY_SPLIT", 0, 0, 1) != 0;
+  c->pol.overlap = gt_overlap();
+  c->verify_split = sig_env().verify_split;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = c->stream.create(hipStreamNonBlocking);
   if (e == hipSuccess) e = c->d_lines.alloc(kNumLines);
@@ -499,24 +503,19 @@ int hg_debug_fp12(hg_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t 
   return HG_OK;
 }
 
+// kernel: a SigForm by its number (bn256_sigform.h), whatever sig_form() would choose
 int hg_sig_pairing_device(hg_ctx* c, const uint8_t* d_sigs, size_t n, uint8_t* d_fe, int kernel, void* stream) {
   if (!c || (n && (!d_sigs || !d_fe)) || n > (size_t)INT32_MAX || kernel < 0 || kernel > 4) return HG_ERR_ARG;
-  if ((kernel == 2 || kernel == 3) && n > (size_t)kSig12MaxN) return HG_ERR_ARG;  // k_sig_lines: 4 n threads in int
+  const SigForm form = (SigForm)kernel;
+  if (sig_form_12(form) && n > (size_t)kSig12MaxN) return HG_ERR_ARG;  // k_sig_lines: 4 n threads in int
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HG_CHECK(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   Submission sub(c, s);
   HG_CHECK(c, sub.start());
-  const bool pad = (kernel & 1) == 0;
-  if (kernel == 4) {
-    launch_sig_pairing_w2(d_sigs, c->flavor, (int)n, c->d_lines.p, (Gt*)d_fe, s);
-  } else if (kernel >= 2) {
-    HG_CHECK(c, c->ws.sig_lines.ensure(sig12_lines_bytes((int)n)));
-    launch_sig_pairing12(d_sigs, c->flavor, (int)n, c->d_lines.p, (Fp*)c->ws.sig_lines.p, (Gt*)d_fe, s, pad);
-  } else {
-    launch_sig_pairing(d_sigs, c->flavor, (int)n, c->d_lines.p, (Gt*)d_fe, s, pad, 0);
-  }
+  HG_CHECK(c, c->ws.sig_lines.ensure(sig_form_ws_bytes(form, (int)n)));
+  if (!launch_sig_form(form, d_sigs, c->flavor, (int)n, c->d_lines.p, c->ws.sig_lines.p, (Gt*)d_fe, s)) return HG_ERR_ARG;
   int rc = check_launch(c);
   if (rc) return rc;
   HG_CHECK(c, sub.finish());

@@ -47,8 +47,9 @@ struct Ws {
   Stream side;
   Event ev_fork, ev_join;
   DevBuf<Gt> gt_fe;
-  // launch_sig_pairing12: the batch's lines evaluated at -sig; launch_verify_split
-  // (config 2): the Miller values and the final exponentiation's records
+  // launch_sig_form's workspace (the 12-lane forms: the batch's lines evaluated
+  // at -sig); launch_verify_split (config 2): the Miller values and the final
+  // exponentiation's records
   DevBuf<uint8_t> sig_lines;
   size_t bytes() const {
     return pts2.bytes() + pts1.bytes() + checks.bytes() + codes_b.bytes() + codes_c.bytes() + order.bytes() +
@@ -141,7 +142,9 @@ struct hg_ctx {
   // the cap a failed device allocation set (gt_cap also follows the table
   // budget; hg_set_table_budget re-derives gt_cap from this)
   int oom_cap = 2;
-  bool overlap = true;  // hg_set_fold_overlap; HG_GT_OVERLAP=0 gives new contexts false
+  // the context's own aggregate submissions: padded, the two-wave form up to
+  // kSigW2MaxN; overlap: hg_set_fold_overlap (HG_GT_OVERLAP=0 gives new contexts false)
+  SigPolicy pol;
   bool verify_split = false;  // hg_set_verify_split; HG_VERIFY_SPLIT=1 gives new contexts true
   // submission order across streams: the event recorded after the last
   // submission and the stream it ran on (the workspaces above are shared)
@@ -166,9 +169,8 @@ struct hg_lane {
   Stream s;
   Event done;
   bool recorded = false;  // `done` marks the lane's last batch
-  bool overlap = true;    // the fold beside the pairing kernel (on ws.side)
-  bool pad = true;        // one pairing wave per SIMD (hg_lane_set_pairing_padding)
-  int w2_max = sig_w2_lane_max();  // the two-wave latency form up to this batch (hg_lane_set_latency_form)
+  // hg_lane_set_pairing_padding, hg_lane_set_latency_form, hg_lane_create's overlap
+  SigPolicy pol{true, sig_env().w2_lane_max, true};
   Event ev_in;  // hg_lane_submit_device: the caller's stream point
   size_t max_batch = 0, max_words = 0;
   HostBuf<uint8_t> h_in;     // pinned staging

@@ -274,6 +274,7 @@ int hg_debug_fp12(hg_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_
  * roofline, the GPU suite's cross-kernel check): d_fe[r] (480 bytes, the
  * engine's internal GT layout) = FE(Miller(G2Base at -sig_r)) for the n
  * 64-byte signature marshals at d_sigs (context flavor), computed by kernel
+ * (the numbers are SigForm's, handel_amd/csrc/bn256_sigform.h)
  * 0: k_verify_sig padded (one wave per SIMD), 1: k_verify_sig unpadded,
  * 2: k_sig_scalars + k_sig_lines + k_verify_sig12 padded, 3: the same
  * unpadded (what a lane in flight runs: since r06 split into k_sig12_miller,

@@ -537,3 +537,53 @@ def test_device_lanes_keep_batches_in_flight(pad):
         for ln in lanes:
             ln.close()
         e.close()
+
+
+def test_pairing_forms_on_partial_waves():
+    """The pairing dispatch at the sizes where a launch can go wrong: batches
+    that end in a partial wave of four 16-lane teams (n = 1, 5, 6, 9) or of
+    five 12-lane teams (n = 1, 4, 6, 9: the padding teams park in the spare
+    records). Each batch runs through the context's own submission (the
+    two-wave form), a padded lane (the 16-lane kernel), a padded lane in the
+    latency form (two-wave again, from the lane's policy) and an unpadded lane
+    (the 12-lane split chain); its last signature is another request's, so its
+    code is HG_ERR_SIG_INVALID. All four code vectors are the expected one and
+    the bitsets pack them."""
+    import torch
+
+    import bench
+    from handel_amd._lib import HG_ERR_SIG_INVALID
+    from handel_amd.distributed import pack_verdicts
+    from handel_amd.engine import DeviceLane
+
+    dev = torch.device("cuda", 0)
+    e = Engine(device=0, flavor="go")
+    lanes = {}
+    try:
+        assert e.set_message(bench.LIB_MESSAGE) == 0
+        reqs, words, sigs, expect, _, _ = bench.make_aggregate_batch(e, 64, 9, seed=11)
+        e.set_aggregate_level(1)
+        assert e.prepare_aggregate() == 0 and e.aggregate_tables() == 1
+        lanes = {"padded": DeviceLane(e, 9), "latency": DeviceLane(e, 9), "unpadded": DeviceLane(e, 9, pad=False)}
+        lanes["latency"].set_latency_form(2048)
+        d_reqs, d_words = bench._dev_bytes(reqs.tobytes(), dev), bench._dev_bytes(words.tobytes(), dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        for n in (1, 4, 5, 6, 9):
+            # the last request gets the signature of a request with another one
+            own = sigs[64 * (n - 1):64 * n]
+            other = next(sigs[64 * j:64 * j + 64] for j in range(9) if sigs[64 * j:64 * j + 64] != own)
+            d_sigs = bench._dev_bytes(sigs[:64 * (n - 1)] + other, dev)
+            want = np.array(expect[:n], dtype=np.int32)
+            want[n - 1] = HG_ERR_SIG_INVALID
+            runs = [("context", e.verify_aggregate_device_bits)] + [(k, ln.submit_device) for k, ln in lanes.items()]
+            for name, run in runs:
+                codes = torch.full((n,), -1, dtype=torch.int32, device=dev)
+                bits = torch.full(((n + 7) // 8,), 0xAA, dtype=torch.uint8, device=dev)
+                run(d_reqs.data_ptr(), n, d_words.data_ptr(), d_sigs.data_ptr(), codes.data_ptr(), bits.data_ptr(), s)
+                torch.cuda.synchronize(dev)
+                assert np.array_equal(codes.cpu().numpy(), want), (name, n)
+                assert torch.equal(bits, pack_verdicts(codes)), (name, n)
+    finally:
+        for ln in lanes.values():
+            ln.close()
+        e.close()

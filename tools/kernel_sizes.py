@@ -4,6 +4,10 @@ extracts the gfx950 code object from the offload bundle in .hip_fatbin and
 lists symbol sizes (llvm-readelf). Build tooling (I-cache footprint check).
 
   python tools/kernel_sizes.py handel_amd/_build/bn256_verify.o
+  python tools/kernel_sizes.py --digest handel_amd/_build/libhandel_gpu.so
+
+--digest lists every function's size and the SHA-256 of its bytes, so a
+refactor can show that a kernel's machine code did not move (diff two runs).
 """
 
 import struct
@@ -57,7 +61,39 @@ def resources(path):
     return out
 
 
+def digests(path):
+    """{device function symbol: (size, SHA-256 of its bytes)} over the gfx950
+    code objects: equal digests in two builds mean equal machine code."""
+    import hashlib
+
+    out = {}
+    for triple, blob in bundles(path):
+        if "gfx950" not in triple:
+            continue
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(blob)
+            f.flush()
+            secs = subprocess.run([LLVM + "llvm-readelf", "-SW", f.name], capture_output=True, text=True).stdout
+            syms = subprocess.run([LLVM + "llvm-readelf", "-sW", f.name], capture_output=True, text=True).stdout
+        where = {}  # section index -> (address, file offset)
+        for line in secs.splitlines():
+            p = line.replace("[", " ").replace("]", " ").split()
+            if len(p) >= 6 and p[0].isdigit() and p[2] in ("PROGBITS", "NOBITS"):
+                where[int(p[0])] = (int(p[3], 16), int(p[4], 16))
+        for line in syms.splitlines():
+            p = line.split()
+            if len(p) >= 8 and p[3] == "FUNC" and p[6].isdigit() and int(p[6]) in where:
+                addr, off = where[int(p[6])]
+                start, size = int(p[1], 16) - addr + off, int(p[2])
+                out[p[7]] = (size, hashlib.sha256(blob[start:start + size]).hexdigest())
+    return out
+
+
 def main():
+    if sys.argv[1] == "--digest":  # one line per function: size, SHA-256, symbol
+        for name, (size, sha) in sorted(digests(sys.argv[2]).items()):
+            print(f"{size:8d}  {sha}  {name}")
+        return
     for triple, blob in bundles(sys.argv[1]):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(blob)
