@@ -261,18 +261,6 @@ HG_DEV void fp_mul3(Fp& r, const Fp& a) {
   fp_add(t, a, a);
   fp_add(r, t, a);
 }
-// normalize a loose value < 2p (limbs < 2^32) into a canonical element
-HG_DEV void fp_norm(Fp& r, const Fp& a) {
-  uint32_t x[10];
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    uint32_t v = a.l[i] + c;
-    x[i] = (i < 9) ? (v & kMask) : v;
-    c = v >> 26;
-  }
-  fp_csub(r, x);
-}
 
 // ---------------------------------------------------------------- conversions
 // 8 LE 32-bit words (a plain integer < 2^256) -> 10 x 26-bit limbs (no reduction)

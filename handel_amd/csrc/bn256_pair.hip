@@ -52,7 +52,8 @@ __global__ __launch_bounds__(64) void k_pair(const PointG1* g1s, const PointG2* 
 // Team Fp12 op probe (parity tests of the building blocks): inputs/outputs are
 // 384-byte GT-marshal-ordered canonical elements.
 //   op 0 a*b, 1 a^2 (merged products), 2 cyclotomic a^2, 3 a^p, 4 a^(p^2),
-//   5 a^-1, 6 conj(a), 7 a^u (cyclotomic), 8 final exponentiation
+//   5 a^-1, 6 conj(a), 7 a^u (cyclotomic), 8 final exponentiation,
+//   10 cyclotomic a^2 by the canonical program (op 2's leaves its result below 2p)
 __global__ __launch_bounds__(64) void k_fp12_op(int op, const uint8_t* a, const uint8_t* b, int n, uint8_t* out) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[kTeamsPerBlock * kTeamWords];
   Team T = make_team(lds, kTeamWords);
@@ -97,9 +98,12 @@ __global__ __launch_bounds__(64) void k_fp12_op(int op, const uint8_t* a, const 
       case 6: t12_conj(T, S_F, S_A); break;
       case 7: t12_pow_u_x<S_F, S_A>(T, S, xh_none()); break;
       case 8: t12_copy(T, S_F, S_A); team_final_exp(T, F, S); break;
-      case 9: t12_sqr_fast(T, S_F, S_A); break;
-      case 10: t12_cyc_sqr(T, S_F, S_A); break;
-      default: t12_copy(T, S_F, S_A); break;
+      case 10:  // the program's one bound instance is I <- C (team_final_exp)
+        t12_copy(T, S_C, S_A);
+        ICyc0<S_I, S_C>::run(T, S, xh_none());
+        t12_copy(T, S_F, S_I);
+        break;
+      default: break;  // launch_fp12_op's caller (hg_debug_fp12) refuses every other op
     }
   }
   if (valid && T.active) {

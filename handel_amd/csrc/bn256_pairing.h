@@ -3,7 +3,7 @@
 // in bn256_pair.hip). One 16-lane team per pairing check (bn256_team.h).
 #pragma once
 #include "bn256_kernels.h"
-#include "bn256_g2team.h"
+#include "bn256_regs.h"
 #include "bn256_xprog.h"
 
 namespace hg {

@@ -34,7 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bn256_decode.h"
-#include "bn256_g2sched.h"
+#include "bn256_regs.h"
 #include "bn256_gt.h"
 #include "bn256_sigfe.h"
 

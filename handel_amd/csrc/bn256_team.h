@@ -1,13 +1,16 @@
-// bn256_team.h — Fp12 arithmetic spread over a 16-lane "team" (one DPP row).
+// bn256_team.h — a 16-lane "team" (one DPP row) and its Fp12 element layout.
 //
 // One pairing check runs on one team. Fp12 = Fp2[w]/(w^6 - xi) is kept flat
 // in the team's LDS region as 12 Fp elements: element e = 2k + c holds
 // component c (0 = x, the i-coefficient; 1 = y, the real part) of the Fp2
-// coefficient of w^k. Lane t < 12 of the team owns element t: for every
-// Fp12 product it accumulates its own output coefficient as a sum of
-// 26-bit-limb partial products in 64-bit columns and reduces ONCE
-// (bn256_fp.h). Lanes 12..15 run the same instruction stream on a clamped
-// index and never store, so the wave stays convergent.
+// coefficient of w^k. Lane t < 12 of the team owns element t. Lanes 12..15
+// run the same instruction stream on a clamped index and never store, so the
+// wave stays convergent.
+//
+// This header holds the team itself, the reductions of a lazy product sum
+// and the element-wise Fp12 operations (conjugate, Frobenius, copy, compare,
+// the inversion of a norm). The Fp12 products and squarings are not here:
+// they are the generated team programs of bn256_xtab.h, run by bn256_xprog.h.
 //
 // The mapping to x/crypto's tower (gfP12{x,y}, gfP6{x,y,z}) is
 // c0=y.z, c1=x.z, c2=y.y, c3=x.y, c4=y.x, c5=x.x; values are identical,
@@ -178,8 +181,8 @@ HG_DEV void fp_reduce8(Fp& r, const uint32_t* x) {
   fp_csub(r, y);  // (the branch-guarded form measured slower here)
 }
 
-// REDC of a lazy sum that carries R-shifted linear terms (acc_add_shifted):
-// those pass through REDC unchanged, so the result is < (products / R) +
+// REDC of a lazy sum that carries R-shifted linear terms (a round's linear
+// terms, bn256_xprog.h): those pass through REDC unchanged, so the result is < (products / R) +
 // (linear terms) + p, below 31p (generator-checked); a quotient estimate
 // (fp_reduce8) makes it canonical. Sums of products only use acc_reduce.
 template <int FROM = 0>
@@ -206,214 +209,6 @@ HG_DEV void acc_reduce_wide_lazy(Fp& r, Acc& a) {
     r.l[i] = (i < 9) ? ((uint32_t)v & kMask) : (uint32_t)v;
     c = v >> 26;
   }
-}
-
-// conditional pieces used by the coefficient kernels
-HG_DEV void fp_sel3(Fp& r, int which, const Fp& a, const Fp& b, const Fp& c) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) r.l[i] = which == 0 ? a.l[i] : (which == 1 ? b.l[i] : c.l[i]);
-}
-
-// Given X (Fp2, reduced) and whether the term wraps (multiply by xi), produce
-// the two left operands u1, u2 for this lane's component so that
-//   comp 0 (x):  out += u1*Y.y + u2*Y.x   with u1 = X'.x, u2 = X'.y
-//   comp 1 (y):  out += u1*Y.y + u2*Y.x   with u1 = X'.y, u2 = -X'.x
-// where X' = X or xi*X = (3x + y, 3y - x). Operands are loose (< 4p).
-HG_DEV void term_operands(Fp& u1, Fp& u2, const Fp2& X, bool wrap, int comp) {
-  Fp nx, ny;
-  fp_neg_loose(nx, X.x);
-  fp_neg_loose(ny, X.y);
-  Fp xpx, xpy, nxpx;
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    uint32_t x = X.x.l[i], y = X.y.l[i];
-    uint32_t wx = 3 * x + y;           // (xi X).x
-    uint32_t wy = 3 * y + nx.l[i];     // (xi X).y = 3y - x
-    uint32_t wnx = 3 * nx.l[i] + ny.l[i];  // -(xi X).x
-    xpx.l[i] = wrap ? wx : x;
-    xpy.l[i] = wrap ? wy : y;
-    nxpx.l[i] = wrap ? wnx : nx.l[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    u1.l[i] = comp ? xpy.l[i] : xpx.l[i];
-    u2.l[i] = comp ? nxpx.l[i] : xpy.l[i];
-  }
-}
-
-// dst = a * b (dst may alias a or b)
-HG_DEV void t12_mul(const Team& T, int dst, int sa, int sb) {
-  const uint32_t* A = slot(T, sa);
-  const uint32_t* B = slot(T, sb);
-  Acc acc;
-  acc_zero(acc);
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    int j = T.k - i;
-    bool wrap = j < 0;
-    j = wrap ? j + 6 : j;
-    Fp2 X, Y;
-    ld_f2(X, A, i);
-    ld_f2(Y, B, j);
-    Fp u1, u2;
-    term_operands(u1, u2, X, wrap, T.comp);
-    acc_mad(acc, u1, Y.y);
-    acc_mad(acc, u2, Y.x);
-  }
-  Fp r;
-  acc_reduce_wide(r, acc);
-  team_sync(T);
-  if (T.active) st_fp(slot(T, dst) + T.e * 10, r);
-  team_sync(T);
-}
-
-HG_DEV void t12_sqr(const Team& T, int dst, int sa) { t12_mul(T, dst, sa, sa); }
-
-// acc += v * R (R = 2^286 = 2^(26*11)): adds the Montgomery-form value v to
-// the product sum, i.e. a linear term costs 10 adds instead of a product.
-HG_DEV void acc_add_shifted(Acc& acc, const Fp& v) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) acc.c[kRedcSteps + i] += v.l[i];
-}
-
-// small constant multiple of a loose element, limb-wise (no carries)
-template <int K>
-HG_DEV void fp_scale(Fp& r, const Fp& a) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) r.l[i] = a.l[i] * K;
-}
-
-// dst = a^2 with the symmetric products merged: lane (k, c) sums 4 terms
-// (i, j, mult, wrap) over pairs i <= j, i + j = k (mod 6), 8 products.
-HG_DEV void t12_sqr_fast(const Team& T, int dst, int sa) {
-  const uint32_t* A = slot(T, sa);
-  // per-k term tables packed 4 bits per k (k = 0..5): i, j, multiplier, wrap flag
-  //   k:      0        1        2        3        4        5
-  //   t=0  (1,5,2,w) (0,1,2)  (0,2,2)  (0,3,2)  (0,4,2)  (0,5,2)
-  //   t=1  (2,4,2,w) (2,5,2,w)(3,5,2,w)(1,2,2)  (1,3,2)  (1,4,2)
-  //   t=2  (0,0,1)   (3,4,2,w)(1,1,1)  (4,5,2,w)(2,2,1)  (2,3,2)
-  //   t=3  (3,3,1,w)  -       (4,4,1,w) -       (5,5,1,w) -
-  const uint32_t I[4] = {0x000001u, 0x111322u, 0x224130u, 0x050403u};
-  const uint32_t J[4] = {0x543215u, 0x432554u, 0x325140u, 0x050403u};
-  const uint32_t M[4] = {0x222222u, 0x222222u, 0x212121u, 0x010101u};  // 0 = dummy term
-  const uint32_t W[4] = {0x000001u, 0x000111u, 0x001010u, 0x010101u};
-  const int sh = 4 * T.k;
-  Acc acc;
-  acc_zero(acc);
-#pragma unroll
-  for (int t = 0; t < 4; t++) {
-    int i = (I[t] >> sh) & 15, j = (J[t] >> sh) & 15;
-    uint32_t m = (M[t] >> sh) & 15;
-    bool wrap = ((W[t] >> sh) & 15) != 0;
-    Fp2 X, Y;
-    ld_f2(X, A, i);
-    ld_f2(Y, A, j);
-    // the multiplier goes on Y: term_operands negates X, which needs X < p
-#pragma unroll
-    for (int l = 0; l < 10; l++) {
-      Y.x.l[l] *= m;
-      Y.y.l[l] *= m;
-    }
-    Fp u1, u2;
-    term_operands(u1, u2, X, wrap, T.comp);
-    acc_mad(acc, u1, Y.y);
-    acc_mad(acc, u2, Y.x);
-  }
-  Fp r;
-  acc_reduce_wide(r, acc);
-  team_sync(T);
-  if (T.active) st_fp(slot(T, dst) + T.e * 10, r);
-  team_sync(T);
-}
-
-// Granger-Scott squaring in the cyclotomic subgroup (valid after the easy part
-// of the final exponentiation). With f = (c0 + c3 s) + (c1 + c4 s) w + (c2 + c5 s) w^2,
-// s = w^3, each group (a, b) squares in Fp4: (a^2 + xi b^2) + 2ab s, and
-//   c0' = 3(a^2 + xi b^2) - 2c0   c3' = 6ab + 2c3      for (a, b) = (c0, c3)
-//   c2' = 3(a^2 + xi b^2) - 2c2   c5' = 6ab + 2c5      for (a, b) = (c1, c4)
-//   c4' = 3(a^2 + xi b^2) - 2c4   c1' = 6 xi ab + 2c1  for (a, b) = (c2, c5)
-// Each lane: 3 products; the +-2c term is added to the high columns.
-HG_DEV void t12_cyc_sqr(const Team& T, int dst, int sa) {
-  const uint32_t* A = slot(T, sa);
-  const int k = T.k;
-  const int ga = (k == 0 || k == 3) ? 0 : ((k == 2 || k == 5) ? 1 : 2);
-  const bool sq = (k & 1) == 0;   // k = 0, 2, 4: the a^2 + xi b^2 lanes
-  const bool xi = (k == 1);       // the 6 xi ab lane
-  const bool cx = T.comp == 0;
-  Fp2 a, b;
-  ld_f2(a, A, ga);
-  ld_f2(b, A, ga + 3);
-  Fp c;
-  ld_fp(c, A + T.e * 10);
-  Fp nax, nay, nbx, da, db, sa_, sb_;
-  fp_neg_loose(nax, a.x);
-  fp_neg_loose(nay, a.y);
-  fp_neg_loose(nbx, b.x);
-  fp_sub(da, a.y, a.x);
-  fp_sub(db, b.y, b.x);
-  fp_add_loose(sa_, a.y, a.x);
-  fp_add_loose(sb_, b.y, b.x);
-  Fp u1, v1, u2, v2, u3;
-#pragma unroll
-  for (int l = 0; l < 10; l++) {
-    // sq lanes: x: (6ax)ay + (18bx)by + (3sb)db ; y: (3sa)da + (6nbx)by + (9sb)db
-    // ab lanes: x: (6ax)by + (6ay)bx ; y: (6ay)by + (6nax)bx
-    // xi lane:  x: 6(3ax+ay)by + 6(3ay+nax)bx ; y: 6(3ay+nax)by + 6(3nax+nay)bx
-    uint32_t xa = 3 * a.x.l[l] + a.y.l[l], xb = 3 * a.y.l[l] + nax.l[l], xc = 3 * nax.l[l] + nay.l[l];
-    uint32_t sq_u1 = cx ? 6 * a.x.l[l] : 3 * sa_.l[l];
-    uint32_t sq_v1 = cx ? a.y.l[l] : da.l[l];
-    uint32_t sq_u2 = cx ? 18 * b.x.l[l] : 6 * nbx.l[l];
-    uint32_t ab_u1 = xi ? 6 * (cx ? xa : xb) : 6 * (cx ? a.x.l[l] : a.y.l[l]);
-    uint32_t ab_u2 = xi ? 6 * (cx ? xb : xc) : 6 * (cx ? a.y.l[l] : nax.l[l]);
-    u1.l[l] = sq ? sq_u1 : ab_u1;
-    v1.l[l] = sq ? sq_v1 : b.y.l[l];
-    u2.l[l] = sq ? sq_u2 : ab_u2;
-    v2.l[l] = sq ? b.y.l[l] : b.x.l[l];
-    u3.l[l] = sq ? (cx ? 3 * sb_.l[l] : 9 * sb_.l[l]) : 0u;
-  }
-  Acc acc;
-  acc_zero(acc);
-  acc_mad(acc, u1, v1);
-  acc_mad(acc, u2, v2);
-  acc_mad(acc, u3, db);
-  // linear term: -2c on the a^2 lanes, +2c on the others (added as 2c R or 2(p - c) R)
-  Fp nc, lin;
-  fp_neg_loose(nc, c);
-  fp_sel(lin, sq, nc, c);
-  fp_scale<2>(lin, lin);
-  acc_add_shifted(acc, lin);
-  Fp r;
-  acc_reduce_wide(r, acc);
-  team_sync(T);
-  if (T.active) st_fp(slot(T, dst) + T.e * 10, r);
-  team_sync(T);
-}
-
-// dst = a * (c + b w + a3 w^3) for line coefficients held in registers
-HG_DEV void t12_mul_line(const Team& T, int dst, int sa, const Fp2& la, const Fp2& lb, const Fp2& lc) {
-  const uint32_t* A = slot(T, sa);
-  Acc acc;
-  acc_zero(acc);
-  // term j = 0 (c), j = 1 (b), j = 3 (a)
-#pragma unroll
-  for (int t = 0; t < 3; t++) {
-    const int jpos = (t == 0) ? 0 : (t == 1 ? 1 : 3);
-    const Fp2& Y = (t == 0) ? lc : (t == 1 ? lb : la);
-    int i = T.k - jpos;
-    bool wrap = i < 0;
-    i = wrap ? i + 6 : i;
-    Fp2 X;
-    ld_f2(X, A, i);
-    Fp u1, u2;
-    term_operands(u1, u2, X, wrap, T.comp);
-    acc_mad(acc, u1, Y.y);
-    acc_mad(acc, u2, Y.x);
-  }
-  Fp r;
-  acc_reduce_wide(r, acc);
-  team_sync(T);
-  if (T.active) st_fp(slot(T, dst) + T.e * 10, r);
-  team_sync(T);
 }
 
 // dst = conj_p6(a): negate odd powers of w (x/crypto gfP12.Conjugate)
@@ -668,23 +463,6 @@ HG_DEV void t12_inv_norm_finish(const Team& T, int s2, const NormTerms& o, const
   team_sync(T);
   if (T.active) st_fp(N + T.e * 10, e);
   team_sync(T);
-}
-
-// dst = a^-1 using scratch slots s1, s2 (x/crypto gfP12.Invert)
-HG_DEV void t12_inv(const Team& T, int dst, int sa, int s1, int s2) {
-  t12_conj(T, s1, sa);          // s1 = conj(a)
-  t12_mul(T, s2, sa, s1);       // s2 = a*conj(a) = N (even coefficients only)
-  t12_inv_norm(T, s2);
-  t12_mul(T, dst, s1, s2);      // conj(a) / N
-}
-
-// dst = a^u (x/crypto gfP12.Exp with the BN parameter u), dst != sa
-HG_DEV void t12_pow_u(const Team& T, int dst, int sa) {
-  t12_copy(T, dst, sa);
-  for (int bit = 61; bit >= 0; bit--) {
-    t12_sqr(T, dst, dst);
-    if ((kU >> bit) & 1) t12_mul(T, dst, dst, sa);
-  }
 }
 
 }  // namespace hg

@@ -576,8 +576,6 @@ template <int D, int A>
 using ISqr12 = XInst<XP_SQR12, D, A>;
 template <int D, int A>
 using ILinePk = XInst<XP_LINE_PK, D, A>;
-template <int D, int A>
-using ILineFix = XInst<XP_LINE_FIX, D, A>;
 template <int PROG>
 using IG2 = XInst<PROG>;
 
@@ -590,11 +588,9 @@ HG_DEV void x_cyc_sqr(const Team& T, XStream& S, XHint h) { ICyc<D, A>::run(T, S
 // dst = a^2 (Miller loop)
 template <int D, int A>
 HG_DEV void x_sqr12(const Team& T, XStream& S, XHint h) { ISqr12<D, A>::run(T, S, h); }
-// dst = a * (LC + LB w + LA w^3) / a * (FC + FB w + FA w^3): the pk / G2Base lines
+// dst = a * (LC + LB w + LA w^3): the pk line
 template <int D, int A>
 HG_DEV void x_line_pk(const Team& T, XStream& S, XHint h) { ILinePk<D, A>::run(T, S, h); }
-template <int D, int A>
-HG_DEV void x_line_fix(const Team& T, XStream& S, XHint h) { ILineFix<D, A>::run(T, S, h); }
 // G2 Miller-loop steps on the register file (x/crypto lineFunctionDouble / Add)
 template <int PROG>
 HG_DEV void x_g2(const Team& T, XStream& S, XHint h) { IG2<PROG>::run(T, S, h); }
@@ -644,13 +640,5 @@ HG_DEV void t12_inv_x(const Team& T, XStream& S, XHint h) {
   t12_inv_norm(T, S2);                                       // S2 = N^-1
   x_mul12<DST, S1, S2>(T, S, h);                             // conj(a) / N
 }
-
-// ------------------------------------------------------------------ layout S (k_verify_sig)
-// The same programs bound to k_verify_sig's compact team region: slots F..G
-// only, registers at kSigRegBase (tools/gen_g2_schedule.py SIG_INSTANCES).
-template <int D, int A, int B>
-using IMul12S = XInst<XP_MUL12_S, D, A, B>;
-template <int D, int A>
-using ICycS = XInst<XP_CYC_SQR_X_S, D, A>;
 
 }  // namespace hg

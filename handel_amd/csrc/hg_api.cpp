@@ -485,6 +485,8 @@ int hg_sign_msg(hg_ctx* c, const uint8_t* msg, size_t len, const uint8_t* scalar
 
 int hg_debug_fp12(hg_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
   if (!c || (n && (!a || !b || !out)) || n > (size_t)INT32_MAX) return HG_ERR_ARG;
+  const int base_op = op & 255;  // bits 8..: repetitions (k_fp12_op)
+  if (base_op > 10 || base_op == 9) return HG_ERR_ARG;
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HG_CHECK(c, hipSetDevice(c->device));

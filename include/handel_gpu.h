@@ -267,7 +267,9 @@ int hg_timing_read_phase(hg_ctx* ctx, int phase, double* total_ms, int* launches
 
 /* Parity probe of the team Fp12 building blocks: elements are 384-byte GT
  * marshals. op: 0 a*b, 1 a^2, 2 cyclotomic a^2, 3 a^p, 4 a^(p^2), 5 a^-1,
- * 6 conj(a), 7 a^u, 8 final exponentiation, 9/10 table-program squarings. */
+ * 6 conj(a), 7 a^u, 8 final exponentiation, 10 cyclotomic a^2 by the
+ * canonical squaring program (9 is retired). Bits 8.. of op: repetitions.
+ * Any other op: HG_ERR_ARG. */
 int hg_debug_fp12(hg_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
 
 /* Kernel probe of the GT path's signature side (bench.py per-kernel

@@ -1,30 +1,30 @@
 #!/usr/bin/env python3
-"""Generates handel_amd/csrc/bn256_g2sched.h: lane-parallel "team programs"
-for a 16-lane team (bn256_g2team.h executes them).
+"""Generates handel_amd/csrc/bn256_xtab.h and bn256_regs.h: lane-parallel
+"team programs" for a 16-lane team (bn256_xprog.h executes them) and the
+numbers of the team's register file.
 
-A program is a short list of rounds. In a round every lane of the team
-computes one Fp element
+A source program (PROGRAMS) is a short list of rounds. In a round every lane
+of the team computes one Fp element
     dst = sum_{slot} (sum_m ca_m * X[ra_m]) * (sum_m cb_m * X[rb_m])
 with small signed integer coefficients and ONE lazy Montgomery reduction,
 then stores it; all lanes run the same instruction stream (only addresses
 and coefficients differ), rounds are separated by a team barrier (every
 lane reads before any lane writes, so in-place programs are fine).
+compile_round turns a round into the two-phase form the kernels run (a
+pre-pass of shared linear combinations, then products and linear terms), and
+bind gives every call site its own table with absolute team element indices.
 
-Operand index space (uint8):
+Operand index space of a source program (uint8):
     0..127    the team's LDS register file F (Fp elements)
     128..139  element e of the program's Fp12 source slot A (2k + c)
     160..171  element e of the program's Fp12 source slot B
 Destination: an F register (< 128), element e of the destination Fp12
 slot (128 + e), or 255 (lane idle).
 
-Programs:
-    DBL, ADD_*     x/crypto optate.go lineFunctionDouble / lineFunctionAdd
-    CYC_SQR        Granger-Scott squaring in the cyclotomic subgroup
-                   (final exponentiation: gfP12.Exp(.., u) squarings)
-    SQR12          Fp12 squaring with the symmetric products merged
-The tables are validated here by interpreting them with plain modular
-arithmetic against the oracle (tests/test_g2_schedule.py repeats this in
-the CPU suite). Build tooling only: nothing in the product imports it.
+The source programs are validated here by interpreting them with plain
+modular arithmetic against the oracle, the compiled and the bound ones down
+to the limb-level model of the reduction (tests/test_g2_schedule.py repeats
+this in the CPU suite). Build tooling only: nothing in the product imports it.
 """
 
 from __future__ import annotations
@@ -35,9 +35,6 @@ import sys
 
 P = 65000549695646603732796438742359905742825358107623003571877145026864184071783
 R_BITS = 286  # Montgomery R = 2^286 (11 REDC digits, bn256_constants.h kRedcSteps)
-R_OVER_P = (1 << R_BITS) / P  # REDC(T) < T/R + p
-MAX_NSLOT = 7
-MAX_TERMS = 6
 SLOT_A = 128
 SLOT_B = 160
 NONE = 255
@@ -47,16 +44,12 @@ FP_SCALARS = ["ZERO", "ONE", "PX", "PY", "SX", "NSY"]
 # The kernels' register file (kG2Regs): the projective Miller-loop programs'
 # point, pk, line coefficients and temporaries. FBX, FCY must stay
 # consecutive (load_fixed_line: the normalised G2Base line, a = 1).
-FP2_RUNTIME = ["X", "Y", "Z", "QX", "QY", "NQY", "P1X", "P1Y", "P2X",
-               "FBX", "FCY", "FB", "FC", "LA", "LB", "LC",
-               # projective doubling temporaries
-               "A", "B", "S", "C", "G",
-               # projective addition temporaries
-               "AB", "S1", "D", "I", "S2", "H", "J", "AV", "L1"]
-# only the Jacobian x/crypto-shaped programs (DBL, ADD_*: generator
-# cross-checks, never run by a kernel) use these; they lie past kG2Regs
-FP2_LEGACY = ["T", "R2", "P1R2", "F2ONE", "F2ZERO", "W", "V", "ET", "ZP", "TPY", "XN", "YJ", "TP", "LA1", "S3"]
-FP2_REGS = FP2_RUNTIME + FP2_LEGACY
+FP2_REGS = ["X", "Y", "Z", "QX", "QY", "NQY", "P1X", "P1Y", "P2X",
+            "FBX", "FCY", "FB", "FC", "LA", "LB", "LC",
+            # projective doubling temporaries
+            "A", "B", "S", "C", "G",
+            # projective addition temporaries
+            "AB", "S1", "D", "I", "S2", "H", "J", "AV", "L1"]
 REG = {}
 for i, n in enumerate(FP_SCALARS):
     REG[n] = i
@@ -64,8 +57,7 @@ _base = len(FP_SCALARS)
 for i, n in enumerate(FP2_REGS):
     REG[n + ".x"] = _base + 2 * i
     REG[n + ".y"] = _base + 2 * i + 1
-NREGS = _base + 2 * len(FP2_REGS)
-NREGS_RUNTIME = _base + 2 * len(FP2_RUNTIME)
+NREGS = _base + 2 * len(FP2_REGS)  # kG2Regs
 assert NREGS <= 128
 # Fp12 source slots: Fp2 coefficient k of slot A is "A{k}", of slot B "B{k}"
 for k in range(6):
@@ -123,23 +115,12 @@ def sq(dst, U):
             Lane(comp(dst, "y"), [(add(uy, ux), add(uy, neg(ux)))])]
 
 
-def mul(dst, U, V, extra=None):
-    """dst (Fp2) = U * V (+ extra * 1, extra an Fp2 lincomb)."""
+def mul(dst, U, V):
+    """dst (Fp2) = U * V."""
     ux, uy = fp2_comp(U, "x"), fp2_comp(U, "y")
     vx, vy = fp2_comp(V, "x"), fp2_comp(V, "y")
-    lx = Lane(comp(dst, "x"), [(ux, vy), (uy, vx)])
-    ly = Lane(comp(dst, "y"), [(uy, vy), (neg(ux), vx)])
-    if extra is not None:
-        lx.slots.append((fp2_comp(extra, "x"), one()))
-        ly.slots.append((fp2_comp(extra, "y"), one()))
-    return [lx, ly]
-
-
-def sq_plus(dst, U, extra):
-    lanes = sq(dst, U)
-    lanes[0].slots.append((fp2_comp(extra, "x"), one()))
-    lanes[1].slots.append((fp2_comp(extra, "y"), one()))
-    return lanes
+    return [Lane(comp(dst, "x"), [(ux, vy), (uy, vx)]),
+            Lane(comp(dst, "y"), [(uy, vy), (neg(ux), vx)])]
 
 
 def smul(dst, U, s_name, k=1):
@@ -180,44 +161,6 @@ def xi_terms(slots_x, slots_y, c):
 def fixed_line_eval(sfx=""):
     # FB = FBX * SX, FC = FCY * NSY  (the G2Base line at -sig), line set sfx
     return smul("FB" + sfx, [("FBX" + sfx, 1)], "SX") + smul("FC" + sfx, [("FCY" + sfx, 1)], "NSY")
-
-
-def prog_double():
-    """lineFunctionDouble(r = (X, Y, Z, T), q = (PX, PY)) -> X,Y,Z,T updated; LA, LB, LC."""
-    r1 = sq("A", [("X", 1)]) + sq("B", [("Y", 1)]) + sq("S", [("Y", 1), ("Z", 1)]) + fixed_line_eval() \
-        + smul("TPY", [("T", 1)], "PY")
-    r2 = (sq("C", [("B", 1)]) + sq("W", [("X", 1), ("B", 1)]) + sq("G", [("A", 3)])
-          + sq("V", [("X", 1), ("A", 3)]) + mul("ET", [("A", 3)], [("T", 1)])
-          + lin("ZP", [("S", 1), ("B", -1), ("T", -1)]))
-    # D = 2(W - A - C); X' = G - 2D; Y' = (D - X') E - 8C = (6W - 6A - 6C - G) 3A - 8C
-    r3 = (mul("Y", [("W", 6), ("A", -6), ("C", -6), ("G", -1)], [("A", 3)], extra=[("C", -8)])
-          + lin("X", [("G", 1), ("W", -4), ("A", 4), ("C", 4)])
-          + sq("T", [("ZP", 1)])
-          + smul("LB", [("ET", -2)], "PX")
-          + mul("LC", [("ZP", 2)], [("TPY", 1)])
-          + lin("LA", [("V", 1), ("A", -1), ("G", -1), ("B", -4)])
-          + lin("Z", [("ZP", 1)]))
-    return [r1, r2, r3]
-
-
-def prog_add(px, py, pr2):
-    """lineFunctionAdd(r = (X,Y,Z,T), p = (px, py), q = (PX, PY), r2 = pr2)."""
-    a1 = mul("AB", [(px, 1)], [("T", 1)]) + sq("S1", [(py, 1), ("Z", 1)]) + fixed_line_eval()
-    # D = (S1 - r2 - T) T ; H = AB - X ; I = H^2 ; S2 = (Z + H)^2
-    a2 = (mul("D", [("S1", 1), (pr2, -1), ("T", -1)], [("T", 1)]) + sq("I", [("AB", 1), ("X", -1)])
-          + sq("S2", [("Z", 1), ("AB", 1), ("X", -1)]) + lin("H", [("AB", 1), ("X", -1)]))
-    # E = 4I ; J = H E ; L1 = D - 2Y ; V = X E ; Z' = S2 - T - I
-    a3 = (mul("J", [("H", 4)], [("I", 1)]) + mul("AV", [("X", 4)], [("I", 1)])
-          + lin("L1", [("D", 1), ("Y", -2)]) + lin("ZP", [("S2", 1), ("T", -1), ("I", -1)]))
-    # X' = L1^2 - J - 2V ; YJ = Y J ; T' = Z'^2 ; b = -2 L1 PX ; c = 2 Z' PY ; LA1 = 2 L1 px ; S3 = (py + Z')^2
-    a4 = (sq_plus("XN", [("L1", 1)], [("J", -1), ("AV", -2)]) + mul("YJ", [("Y", 1)], [("J", 1)])
-          + sq("TP", [("ZP", 1)]) + smul("LB", [("L1", -2)], "PX") + smul("LC", [("ZP", 2)], "PY")
-          + mul("LA1", [("L1", 2)], [(px, 1)]) + sq("S3", [(py, 1), ("ZP", 1)]))
-    # Y' = (V - X') L1 - 2 YJ ; a = LA1 - (S3 - r2 - T') ; X, Z, T <- X', Z', T'
-    a5 = (mul("Y", [("AV", 1), ("XN", -1)], [("L1", 1)], extra=[("YJ", -2)])
-          + lin("LA", [("LA1", 1), ("S3", -1), (pr2, 1), ("TP", 1)])
-          + lin("X", [("XN", 1)]) + lin("Z", [("ZP", 1)]) + lin("T", [("TP", 1)]))
-    return [a1, a2, a3, a4, a5]
 
 
 # ---- homogeneous projective G2 steps (the Miller loop's point R lives in X, Y, Z
@@ -549,11 +492,6 @@ def prog_line_n(lb, lc):
 
 
 PROGRAMS = {
-    "DBL": prog_double(),
-    "ADD_POS": prog_add("QX", "QY", "R2"),
-    "ADD_NEG": prog_add("QX", "NQY", "R2"),
-    "ADD_F1": prog_add("P1X", "P1Y", "P1R2"),
-    "ADD_F2": prog_add("P2X", "QY", "R2"),
     "CYC_SQR": prog_cyc_sqr(),
     "SQR12": prog_sqr12(),
     "MUL12": prog_mul12(),
@@ -584,38 +522,9 @@ PROGRAMS["SQR12_12"] = prog_sqr12()
 PROGRAMS["LINE_FIX_12"] = prog_line_n("FB", "FC")
 PROGRAMS["MUL12_12"] = prog_mul12()
 PROGRAMS["CYC_SQR_X_12"] = prog_cyc_sqr_x_shared()  # r06: 24 pre-pass values (two per lane)
-# programs also emitted in the single-phase table format (bn256_g2sched.h)
-LEGACY = ("DBL", "ADD_POS", "ADD_NEG", "ADD_F1", "ADD_F2", "CYC_SQR", "SQR12")
 
 
-# ------------------------------------------------------------------ checks + interpreter
-def bound(terms):
-    return sum(abs(k) for _, k in terms)
-
-
-def check_round(lanes, name):
-    assert len(lanes) <= 16, f"{name}: {len(lanes)} lanes"
-    dsts = [l.dst for l in lanes]
-    assert len(set(dsts)) == len(dsts), f"{name}: duplicate destinations"
-    worst = 0
-    for l in lanes:
-        assert len(l.slots) <= MAX_NSLOT, f"{name}: {len(l.slots)} slots"
-        t = 0
-        for a, b in l.slots:
-            assert len(a) <= MAX_TERMS and len(b) <= MAX_TERMS, f"{name}: too many terms {a} {b}"
-            # int32 limb sums in g2_lincomb: |v + K p_i| <= (pos + neg) * 2^26 < 2^31
-            for terms in (a, b):
-                pos = sum(k for _, k in terms if k > 0)
-                negs = sum(-k for _, k in terms if k < 0)
-                assert pos + negs <= 30, f"{name}: coefficient range {terms}"
-            t += bound(a) * bound(b)
-        # REDC output < (t / R_OVER_P + 1) p must stay below 2p (acc_reduce + csub)
-        assert t / R_OVER_P + 1 < 2, f"{name}: product bound {t}"
-        # 64-bit columns: limbs < 2^26 * sum|c|; 10 terms per column per slot
-        worst = max(worst, t)
-    return worst
-
-
+# ------------------------------------------------------------------ source-program interpreter
 def run_program(prog, F):
     """Interprets a program on an index -> residue map (plain values mod p)."""
     for lanes in prog:
@@ -632,44 +541,16 @@ def run_program(prog, F):
 
 
 def validate(seed=1):
+    """The source programs of the Fp12 squarings against the oracle, lane by lane."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     from oracle import bn256_oracle as O
 
     rng = random.Random(seed)
-    for name, prog in PROGRAMS.items():
-        if name not in LEGACY:
-            continue
-        for i, r in enumerate(prog):
-            check_round(r, f"{name}[{i}]")
     for trial in range(3):
-        Q = O.g2_mul(O.G2_GEN, rng.randrange(1, O.ORDER))
-        Hp = O.g1_mul(O.G1_GEN, rng.randrange(1, O.ORDER))
-        Rj = O.jac_mul(O.FP2_OPS, O.to_jac(O.FP2_OPS, Q), rng.randrange(2, 1000))
-        r = (Rj[0], Rj[1], Rj[2], O.f2_sqr(Rj[2]))
         F = {i: rng.randrange(P) for i in list(range(NREGS)) + list(range(SLOT_A, SLOT_A + 12))
              + list(range(SLOT_B, SLOT_B + 12))}
         F[REG["ZERO"]] = 0
         F[REG["ONE"]] = 1
-        F[REG["PX"]], F[REG["PY"]] = Hp
-
-        def put(n, v):
-            F[comp(n, "x")], F[comp(n, "y")] = v
-
-        for n, v in zip(("X", "Y", "Z", "T"), r):
-            put(n, v)
-        put("QX", Q[0])
-        put("QY", Q[1])
-        put("NQY", O.f2_neg(Q[1]))
-        put("R2", O.f2_sqr(Q[1]))
-        a, b, c, r_new = O._line_double(r, *Hp)
-        G = run_program(PROGRAMS["DBL"], dict(F))
-        assert [(G[comp(n, "x")], G[comp(n, "y")]) for n in ("X", "Y", "Z", "T")] == list(r_new), "DBL point"
-        assert [(G[comp(n, "x")], G[comp(n, "y")]) for n in ("LA", "LB", "LC")] == [a, b, c], "DBL line"
-        for prog, pq in (("ADD_POS", (Q[0], Q[1])), ("ADD_NEG", (Q[0], O.f2_neg(Q[1])))):
-            a, b, c, r_new = O._line_add(r, pq, *Hp, O.f2_sqr(pq[1]))
-            G = run_program(PROGRAMS[prog], dict(F))
-            assert [(G[comp(n, "x")], G[comp(n, "y")]) for n in ("X", "Y", "Z", "T")] == list(r_new), prog
-            assert [(G[comp(n, "x")], G[comp(n, "y")]) for n in ("LA", "LB", "LC")] == [a, b, c], prog + " line"
         # Fp12 squarings: a random element, and a cyclotomic one
         f = [(rng.randrange(P), rng.randrange(P)) for _ in range(6)]
         cyc = O.f12_mul(O.f12_conj(f), O.f12_inv(f))
@@ -1118,7 +999,9 @@ def run_xprogram(rounds, F, A=None, B=None, limbs=False):
 
 
 def validate_x(seed=2):
-    """The compiled programs against the oracle (same cases as validate())."""
+    """The compiled programs against the oracle: the projective G2 steps and
+    their lines against x/crypto's lineFunctionDouble / lineFunctionAdd, the
+    Fp12 products and squarings against the tower arithmetic."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     from oracle import bn256_oracle as O
 
@@ -1140,12 +1023,9 @@ def validate_x(seed=2):
         def getf(G, n):
             return (G[comp(n, "x")], G[comp(n, "y")])
 
-        for n, v in zip(("X", "Y", "Z", "T"), r):
-            put(F, n, v)
         put(F, "QX", Q[0])
         put(F, "QY", Q[1])
         put(F, "NQY", O.f2_neg(Q[1]))
-        put(F, "R2", O.f2_sqr(Q[1]))
         # projective steps: R as (x Z : y Z : Z) with Z = xi W for a random W
         xi = (1, 3)
         aff = lambda j: (O.f2_mul(j[0], O.f2_inv(O.f2_sqr(j[2]))),  # noqa: E731
@@ -1266,9 +1146,9 @@ F_BASE = 12 * len(SLOTS)
 FOLD_F_BASE = 12 * (SLOTS.index("B") + 1)
 F_BASE_CTX = {"FE": F_BASE, "ML": F_BASE, "FOLD": FOLD_F_BASE}
 SCR_BASE = {"FE": F_BASE + 2, "ML": 12 * SLOTS.index("C"), "FOLD": FOLD_F_BASE + 2}
-REGION_END = {"FE": F_BASE + NREGS_RUNTIME, "ML": F_BASE + NREGS_RUNTIME,
+REGION_END = {"FE": F_BASE + NREGS, "ML": F_BASE + NREGS,
               "FOLD": FOLD_F_BASE + 2 + SCRATCH_CAP["FOLD"]}
-assert SCR_BASE["FE"] + SCRATCH_CAP["FE"] <= F_BASE + NREGS_RUNTIME
+assert SCR_BASE["FE"] + SCRATCH_CAP["FE"] <= F_BASE + NREGS
 
 
 def _pow_u_mul_instances(dst, sa):
@@ -1377,13 +1257,13 @@ def bind(xr, binding, ctx, layout=""):
     region_end = REGION_END[ctx]
     if layout == "S":
         assert ctx in SIG_SCR_BASE and all(b in SIG_SLOTS for b in binding), "layout S: slots F..G only"
-        sbase, fbase, region_end = SIG_SCR_BASE[ctx], SIG_F_BASE, SIG_F_BASE + NREGS_RUNTIME
+        sbase, fbase, region_end = SIG_SCR_BASE[ctx], SIG_F_BASE, SIG_F_BASE + NREGS
     if layout == "T":
         assert ctx in SIG_T_SCR_BASE and all(b in SIG_T_SLOTS for b in binding), "layout T: slots F..D only"
-        sbase, fbase, region_end = SIG_T_SCR_BASE[ctx], SIG_T_F_BASE, SIG_T_F_BASE + NREGS_RUNTIME
+        sbase, fbase, region_end = SIG_T_SCR_BASE[ctx], SIG_T_F_BASE, SIG_T_F_BASE + NREGS
     if layout == "V":
         assert ctx == "ML" and all(b == "F" for b in binding), "layout V: the Miller loop on slot F"
-        sbase, fbase, region_end = 12, V_F_BASE, V_F_BASE + NREGS_RUNTIME
+        sbase, fbase, region_end = 12, V_F_BASE, V_F_BASE + NREGS
 
     def src(code):
         if code >= X_SCR:
@@ -1683,7 +1563,7 @@ def emit_x(X, path):
     sig_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "S"}, key=list(X_PROGRAMS).index)
     sig_t_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "T"}, key=list(X_PROGRAMS).index)
     v_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "V"}, key=list(X_PROGRAMS).index)
-    v_end = V_F_BASE + NREGS_RUNTIME
+    v_end = V_F_BASE + NREGS
     lines = ["// Generated by tools/gen_g2_schedule.py — do not edit.",
              "// Two-phase team programs executed by bn256_xprog.h (encoding: see there),",
              "// one table per call-site instance (absolute team element indices).",
@@ -1745,58 +1625,14 @@ def emit_x(X, path):
     return len(words)
 
 
-# ------------------------------------------------------------------ emit
-def emit(path):
+def emit_regs(path):
+    """bn256_regs.h: the numbers of the team's register file (REG)."""
     lines = ["// Generated by tools/gen_g2_schedule.py — do not edit.",
-             "// Lane-parallel team programs (see the generator for the encoding).",
-             "#pragma once", "#include <stdint.h>", "namespace hg {",
-             f"static constexpr int kG2Regs = {NREGS_RUNTIME};  // the kernels' register file",
-             f"static constexpr int kG2RegsAll = {NREGS};  // + the Jacobian cross-check programs' registers",
-             f"static constexpr int kG2MaxSlots = {MAX_NSLOT};",
-             f"static constexpr int kG2MaxTerms = {MAX_TERMS};", f"static constexpr uint8_t kG2None = {NONE};",
-             f"static constexpr int kOpSlotA = {SLOT_A};", f"static constexpr int kOpSlotB = {SLOT_B};"]
-    for k, v in REG.items():
-        if v < 128:
-            lines.append(f"static constexpr int R_{k.replace('.', '_')} = {v};")
-    lines.append(f"struct G2Lane {{\n  uint8_t dst, pad[3];\n  uint8_t ar[{MAX_NSLOT}][{MAX_TERMS}];\n"
-                 f"  int8_t ac[{MAX_NSLOT}][{MAX_TERMS}];\n  uint8_t br[{MAX_NSLOT}][{MAX_TERMS}];\n"
-                 f"  int8_t bc[{MAX_NSLOT}][{MAX_TERMS}];\n}};")
-    lines.append(f"struct G2Round {{\n  int nslot, nta[{MAX_NSLOT}], ntb[{MAX_NSLOT}], first;  // first = index into kG2Lanes\n}};")
-    all_lanes = []
-    rounds = {}
-    for name, prog in PROGRAMS.items():
-        if name not in LEGACY:
-            continue
-        rounds[name] = []
-        for r in prog:
-            nslot = max(len(l.slots) for l in r)
-            nta = [max((len(l.slots[s][0]) if s < len(l.slots) else 0) for l in r) for s in range(MAX_NSLOT)]
-            ntb = [max((len(l.slots[s][1]) if s < len(l.slots) else 0) for l in r) for s in range(MAX_NSLOT)]
-            rounds[name].append((nslot, nta, ntb, len(all_lanes)))
-            for t in range(16):
-                l = r[t] if t < len(r) else None
-                ent = {"dst": l.dst if l else NONE, "ar": [], "ac": [], "br": [], "bc": []}
-                for s in range(MAX_NSLOT):
-                    a, b = (l.slots[s] if (l and s < len(l.slots)) else ([], []))
-                    pa = list(a) + [(REG["ZERO"], 0)] * (MAX_TERMS - len(a))
-                    pb = list(b) + [(REG["ZERO"], 0)] * (MAX_TERMS - len(b))
-                    ent["ar"].append([x for x, _ in pa])
-                    ent["ac"].append([k for _, k in pa])
-                    ent["br"].append([x for x, _ in pb])
-                    ent["bc"].append([k for _, k in pb])
-                all_lanes.append(ent)
-
-    def arr(v):
-        return "{" + ", ".join(arr(x) if isinstance(x, list) else str(x) for x in v) + "}"
-
-    lines.append(f"__constant__ static const G2Lane kG2Lanes[{len(all_lanes)}] = {{")
-    for e in all_lanes:
-        lines.append(f"  {{{e['dst']}, {{0, 0, 0}}, {arr(e['ar'])}, {arr(e['ac'])}, {arr(e['br'])}, {arr(e['bc'])}}},")
-    lines.append("};")
-    for name, rs in rounds.items():
-        body = ", ".join(f"{{{n}, {arr(a)}, {arr(b)}, {f}}}" for n, a, b, f in rs)
-        lines.append(f"static constexpr int kProg{name}Len = {len(rs)};")
-        lines.append(f"static constexpr G2Round kProg{name}[{len(rs)}] = {{{body}}};")
+             "// The team's LDS register file: Fp element numbers of the scalars and of",
+             "// the Fp2 registers' components (the team programs' operands, bn256_xtab.h).",
+             "#pragma once", "namespace hg {",
+             f"static constexpr int kG2Regs = {NREGS};"]
+    lines += [f"static constexpr int R_{k.replace('.', '_')} = {v};" for k, v in REG.items() if v < NREGS]
     lines.append("}  // namespace hg")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -1805,11 +1641,11 @@ def emit(path):
 if __name__ == "__main__":
     validate()
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "handel_amd", "csrc")
-    emit(os.path.join(csrc, "bn256_g2sched.h"))
+    emit_regs(os.path.join(csrc, "bn256_regs.h"))
     Xp = validate_x()
     check_instances(Xp)
     nwords = emit_x(Xp, os.path.join(csrc, "bn256_xtab.h"))
     print(len(ALL_INSTANCES), "instances,", nwords * 4, "table bytes")
     for name, rounds in Xp.items():
         print(name, [(r.nv, r.nt, r.np, r.nl, r.words()) for r in rounds])
-    print("validated and wrote bn256_g2sched.h, bn256_xtab.h")
+    print("validated and wrote bn256_regs.h, bn256_xtab.h")
