@@ -47,6 +47,7 @@ struct GtWork {
   int chunk_grid;  // workgroups of k_gt_chunks (one wave: kGtChunkTeams teams)
   int chunk;       // terms per chunk
   int win_bits;    // 8 or 16: which window table `win` is
+  bool torus;      // `win` (16-key) and `blk` are in torus form: k_tor_chunks, y[r] = X
 };
 
 // G_i = e(H, pk_i) for the n registry keys
@@ -81,6 +82,17 @@ bool launch_sig_form(SigForm f, const uint8_t* sigs, int flavor, int n, const Li
 // (launch_verify_split); ws: fe12_ws_bytes(n) bytes. false as launch_sig_form
 size_t fe12_ws_bytes(int n);
 bool launch_fe12(Gt* fe, int n, uint8_t* ws, hipStream_t s);
+// The torus form of the 16-key window table (nwin entries) and the block table
+// (nblk): each entry g = a + b w becomes alpha = (1 + a)/b in its first six
+// elements, zero in the rest (bn256_gt.hip). launch_tor_scan: *flag = 1 when an
+// entry has no alpha (b = 0), else 0; nothing is written. launch_tor_convert:
+// in place, only after a clean scan. A fold over converted tables (GtWork.torus)
+// leaves y[r] = X with e(H, aggregate key)'s conjugate = X/conj(X), which only
+// launch_tor_compare reads: fe[r] conj(X) == X for every request still HG_OK,
+// and (bits non-null) the verdict bitset as launch_gt_compare_bits writes it.
+void launch_tor_scan(Gt* win, size_t nwin, Gt* blk, size_t nblk, int nreg, int* flag, hipStream_t s);
+void launch_tor_convert(Gt* win, size_t nwin, Gt* blk, size_t nblk, int nreg, hipStream_t s);
+void launch_tor_compare(const Gt* fe, const Gt* x, int n, int32_t* codes, uint8_t* bits, hipStream_t s);
 void launch_gt_compare(const Gt* fe, const Gt* y, int n, int32_t* codes, hipStream_t s);
 // the same, and the verdict bitset (ceil(n / 8) bytes, hg_pack_verdicts_device's layout)
 void launch_gt_compare_bits(const Gt* fe, const Gt* y, int n, int32_t* codes, uint8_t* bits, hipStream_t s);

@@ -595,6 +595,330 @@ __global__ __launch_bounds__(64) void k_gt_compare_bits(const Gt* fe, const Gt* 
   if (l == 0) bits[b] = (uint8_t)(m & 0xffu);
 }
 
+// ------------------------------------------------------------------ torus form of the fold's tables
+// A table entry is unitary: g = a + b w with a, b in Fp6 = Fp2[v]/(v^3 - xi)
+// (v = w^2: a holds the even powers of w, b the odd ones) and g conj(g) = 1,
+// so g = (alpha + w)/(alpha - w) with alpha = (1 + a)/b. The 16-key window
+// table and the block table keep alpha in the first six elements of each
+// entry (the entry stride stays sizeof(Gt); the other six are zero). A running
+// product is any X in Fp12 with value X/conj(X): a term multiplies it by
+// (alpha + w), two Fp6 products (TORMULF) instead of an Fp12 product; the
+// conjugate of a term is -alpha; partial products combine by the plain Fp12
+// product (k_gt_combine, unchanged); and the check fe == X/conj(X) is
+// fe conj(X) == X (k_tor_compare_bits), so nothing is inverted per request.
+// g = +-1 (b = 0) has no alpha: k_tor_scan finds such entries before anything
+// is written, and a table set with one stays in Fp12 form (k_gt_chunks).
+struct Fp6 {
+  Fp2 c[3];  // c0 + c1 v + c2 v^2
+};
+HG_DEV void f6_mul(Fp6& r, const Fp6& a, const Fp6& b) {
+  Fp2 t0, t1, t2, s, u, w;
+  Fp6 o;
+  f2_mul(t0, a.c[0], b.c[0]);
+  f2_mul(t1, a.c[1], b.c[1]);
+  f2_mul(t2, a.c[2], b.c[2]);
+  f2_add(s, a.c[1], a.c[2]);
+  f2_add(u, b.c[1], b.c[2]);
+  f2_mul(w, s, u);
+  f2_sub(w, w, t1);
+  f2_sub(w, w, t2);
+  f2_mul_xi(w, w);
+  f2_add(o.c[0], t0, w);  // t0 + xi (a1 b2 + a2 b1)
+  f2_add(s, a.c[0], a.c[1]);
+  f2_add(u, b.c[0], b.c[1]);
+  f2_mul(w, s, u);
+  f2_sub(w, w, t0);
+  f2_sub(w, w, t1);
+  f2_mul_xi(s, t2);
+  f2_add(o.c[1], w, s);  // a0 b1 + a1 b0 + xi t2
+  f2_add(s, a.c[0], a.c[2]);
+  f2_add(u, b.c[0], b.c[2]);
+  f2_mul(w, s, u);
+  f2_sub(w, w, t0);
+  f2_sub(w, w, t2);
+  f2_add(o.c[2], w, t1);  // a0 b2 + a2 b0 + t1
+  r = o;
+}
+// The inverse of a != 0 as adj / n: adj = a^(p^2) a^(p^4) in Fp6 and the norm
+// n = a adj in Fp2, n != 0.
+HG_DEV void f6_adj_norm(Fp6& adj, Fp2& n, const Fp6& a) {
+  Fp2 A, B, C, t;
+  f2_sqr(A, a.c[0]);
+  f2_mul(t, a.c[1], a.c[2]);
+  f2_mul_xi(t, t);
+  f2_sub(A, A, t);  // a0^2 - xi a1 a2
+  f2_sqr(B, a.c[2]);
+  f2_mul_xi(B, B);
+  f2_mul(t, a.c[0], a.c[1]);
+  f2_sub(B, B, t);  // xi a2^2 - a0 a1
+  f2_sqr(C, a.c[1]);
+  f2_mul(t, a.c[0], a.c[2]);
+  f2_sub(C, C, t);  // a1^2 - a0 a2
+  f2_mul(n, a.c[2], B);
+  f2_mul(t, a.c[1], C);
+  f2_add(n, n, t);
+  f2_mul_xi(n, n);
+  f2_mul(t, a.c[0], A);
+  f2_add(n, n, t);  // a0 A + xi (a2 B + a1 C)
+  adj.c[0] = A;
+  adj.c[1] = B;
+  adj.c[2] = C;
+}
+// one 8-byte aligned element of an entry
+HG_DEV void tor_ld(Fp& v, const uint32_t* p) {
+  const uint2* src = (const uint2*)__builtin_assume_aligned(p, 8);
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const uint2 x = src[i];
+    v.l[2 * i] = x.x;
+    v.l[2 * i + 1] = x.y;
+  }
+}
+HG_DEV void tor_st(uint32_t* p, const Fp& v) {
+  uint2* dst = (uint2*)__builtin_assume_aligned(p, 8);
+#pragma unroll
+  for (int i = 0; i < 5; i++) dst[i] = make_uint2(v.l[2 * i], v.l[2 * i + 1]);
+}
+// the Fp6 halves of an entry: odd = 0 the even powers of w (a), 1 the odd ones (b)
+HG_DEV void tor_load_half(Fp6& r, const Gt* g, int odd) {
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    tor_ld(r.c[m].x, g->w + 20 * (2 * m + odd));
+    tor_ld(r.c[m].y, g->w + 20 * (2 * m + odd) + 10);
+  }
+}
+// The entries the conversion walks: the 16-key window table, then the block
+// table. A window entry whose subset holds none of the registry's keys (the
+// empty subset; in a ragged last window also its copies) is 1 and no request
+// names it: it is skipped and keeps its bytes.
+struct TorTables {
+  Gt* win;
+  Gt* blk;
+  size_t nwin, nblk;  // entries
+  int nreg;
+};
+HG_DEV Gt* tor_entry(const TorTables& t, size_t idx) {
+  if (idx < t.nwin) {
+    const int w = (int)(idx >> 16), have = min(16, t.nreg - 16 * w);
+    return ((uint32_t)idx & ((1u << have) - 1u) & 0xffffu) ? t.win + idx : nullptr;
+  }
+  return idx < t.nwin + t.nblk ? t.blk + (idx - t.nwin) : nullptr;
+}
+// flag |= 1 when an entry has b = 0 (nothing is written)
+__global__ __launch_bounds__(256) void k_tor_scan(TorTables t, int* flag) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const Gt* g = tor_entry(t, idx);
+  if (!g) return;
+  uint32_t any = 0;
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    const uint4* p = reinterpret_cast<const uint4*>(g->w + 20 * (2 * m + 1));  // 80-byte offsets of a 16-aligned entry
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+      const uint4 v = p[i];
+      any |= v.x | v.y | v.z | v.w;
+    }
+  }
+  if (any == 0) atomicOr(flag, 1);
+}
+// In place, one thread per run of kTorRun consecutive entries. With
+// b^-1 = adj(b) / n(b), n in Fp2, alpha = (1 + a) adj(b) / n(b): the forward
+// pass leaves M = (1 + a) adj(b) in elements 0..5 of the entry, n in elements
+// 6, 7 and the product of the run's earlier norms in elements 8, 9; one Fp2
+// inversion per run (Montgomery's trick over the norms); the backward pass
+// writes alpha = M / n to elements 0..5 and zero to the rest.
+static constexpr int kTorRun = 16;
+__global__ __launch_bounds__(64) void k_tor_convert(TorTables t) {
+  const size_t first = ((size_t)blockIdx.x * 64 + threadIdx.x) * kTorRun;
+  Fp2 acc;
+  f2_one(acc);
+#pragma unroll 1
+  for (int i = 0; i < kTorRun; i++) {
+    Gt* g = tor_entry(t, first + i);
+    if (!g) continue;
+    Fp6 a, b, adj;
+    Fp2 n;
+    tor_load_half(b, g, 1);
+    f6_adj_norm(adj, n, b);
+    tor_load_half(a, g, 0);
+    Fp one;
+    fp_one(one);
+    fp_add(a.c[0].y, a.c[0].y, one);
+    f6_mul(a, a, adj);
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+      tor_st(g->w + 20 * m, a.c[m].x);
+      tor_st(g->w + 20 * m + 10, a.c[m].y);
+    }
+    tor_st(g->w + 60, n.x);
+    tor_st(g->w + 70, n.y);
+    tor_st(g->w + 80, acc.x);
+    tor_st(g->w + 90, acc.y);
+    f2_mul(acc, acc, n);
+  }
+  Fp2 inv;
+  f2_inv(inv, acc);
+  Fp zero;
+  fp_zero(zero);
+#pragma unroll 1
+  for (int i = kTorRun - 1; i >= 0; i--) {
+    Gt* g = tor_entry(t, first + i);
+    if (!g) continue;
+    Fp2 n, pre, ni;
+    tor_ld(n.x, g->w + 60);
+    tor_ld(n.y, g->w + 70);
+    tor_ld(pre.x, g->w + 80);
+    tor_ld(pre.y, g->w + 90);
+    f2_mul(ni, inv, pre);  // 1 / n_i
+    f2_mul(inv, inv, n);   // the inverse of the product before i
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+      Fp2 c;
+      tor_ld(c.x, g->w + 20 * m);
+      tor_ld(c.y, g->w + 20 * m + 10);
+      f2_mul(c, c, ni);
+      tor_st(g->w + 20 * m, c.x);
+      tor_st(g->w + 20 * m + 10, c.y);
+    }
+#pragma unroll
+    for (int e = 6; e < 12; e++) tor_st(g->w + 10 * e, zero);
+  }
+}
+
+using ITorF = XInst<XP_TORMULF, S_A, S_A, S_B>;  // A = A * (alpha + w), alpha in elements 0..5 of B
+HG_DEV void tor_mul(const Team& T, XStream& S) {
+  team_sync();
+  ITorF::run(T, S, xh<ITorF>());
+}
+// element e of a torus entry (e < 6)
+HG_DEV void tor_read(Fp& v, const Gt* g, int e) { tor_ld(v, g->w + 10 * e); }
+// lanes 0..5: element tl of slot B = +-alpha
+HG_DEV void tor_put(const Team& T, const Fp& v0, bool conj) {
+  Fp v = v0, n;
+  fp_neg(n, v);
+  fp_sel(v, conj, n, v);
+  if (T.tl < 6) st_fp_a8(slot(T, S_B) + T.tl * 10, v.l);
+}
+
+// k_gt_chunks on a table set in torus form: the same plan, term lists, order
+// and read pipeline; a team's X starts as +-alpha + w of its first term and
+// takes every further term by TORMULF. Lanes 0..5 read the 240 bytes of a
+// term. A team whose chunk is shorter than the wave's longest has no "one" to
+// multiply by (one has no finite alpha): in such a round each lane keeps its
+// element of X in slot F, which no fold program touches, and puts it back
+// after the product.
+__global__ __launch_bounds__(64, HG_CHUNK_WAVES) void k_tor_chunks(const Gt* win, const Gt* blk, const uint32_t* terms,
+                                                   const int2* ord, int cap, const GtReq* plan, const GtHdr* hdr,
+                                                   int chunk, Gt* partial, Gt* y) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kTeams12 * kFoldWords];
+  Team T = make_team12(lds, kFoldWords);  // five 12-lane teams per wave
+  fold_regs_init(T);
+  const int team = team12_index();
+  const int total = hdr->chunks, nlong = hdr->nlong;
+  const bool rd = T.tl < 6;
+  XStream S = x_stream();
+  for (int base = blockIdx.x * kTeams12; base < total; base += gridDim.x * kTeams12) {  // wave-uniform
+    const int k = base + team;
+    const bool valid = k < total && T.active;
+    int first = 0, cnt = 0, r = 0, c = 0;
+    bool single = false;
+    if (valid) {
+      const int2 e = k < nlong ? ord[k] : ord[cap - 1 - (k - nlong)];
+      c = e.x;
+      r = e.y;
+      const GtReq g = plan[r];
+      first = g.term_off + (c - g.chunk_off) * chunk;
+      cnt = min(chunk, g.term_off + g.m - first);
+      single = g.chunks == 1;
+    }
+    int maxc = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) maxc = max(maxc, __shfl_xor(maxc, d));
+    const uint32_t my_t = T.tl < cnt ? terms[first + T.tl] : 0u;
+    const int tbase = 12 * team;
+    auto term = [&](int i) -> uint32_t {  // wave-uniform i: every lane runs the shuffle
+      const uint32_t v = (uint32_t)__shfl((int)my_t, tbase + (i < 12 ? i : 0), 64);
+      return i < 12 ? v : (i < cnt ? terms[first + i] : 0u);
+    };
+    // X = +-alpha + w: element 2k + c of an even k is alpha's element k + c,
+    // element 3 (the real part of w's coefficient) is one, the rest zero
+    Fp cur, n1, n2, one;
+    fp_one(one);
+    fp_zero(cur);
+    fp_zero(n1);
+    fp_zero(n2);
+    const uint32_t t0 = term(0);
+    const bool even = (T.k & 1) == 0;
+    if (valid && even) tor_read(cur, term_ptr(t0, win, blk), T.k + T.comp);
+    {
+      Fp n;
+      fp_neg(n, cur);
+      fp_sel(cur, (t0 & kTermConj) != 0, n, cur);
+      fp_sel(cur, T.e == 3, one, cur);
+    }
+    if (T.active) st_fp_a8(slot(T, S_A) + T.e * 10, cur.l);
+    uint32_t t1 = term(1), t2 = term(2);
+    if (1 < cnt && rd) tor_read(n1, term_ptr(t1, win, blk), T.tl);
+    if (2 < cnt && rd) tor_read(n2, term_ptr(t2, win, blk), T.tl);
+#pragma unroll 1
+    for (int i = 1; i < maxc; i++) {
+      const bool pad = i >= cnt;
+      tor_put(T, n1, (t1 & kTermConj) != 0);
+      n1 = n2;
+      t1 = t2;
+      t2 = term(i + 2);
+      if (i + 2 < cnt && rd) tor_read(n2, term_ptr(t2, win, blk), T.tl);
+      if (pad) lds_fp12_copy(T, slot(T, S_F), slot(T, S_A));
+      tor_mul(T, S);
+      team_sync();
+      if (pad) lds_fp12_copy(T, slot(T, S_A), slot(T, S_F));
+    }
+    team_sync();
+    if (valid) gt_store(T, S_A, single ? y + r : partial + c);
+    team_sync();
+  }
+}
+
+// The comparison on a table set in torus form: x[r] is the fold's X, and
+// fe[r] == X/conj(X) <=> fe[r] conj(X) == X (both sides canonical: word
+// equality), one 16-lane team per request and MUL12F. Codes and (bits
+// non-null) the verdict bitset as k_gt_compare_bits writes them: one
+// workgroup per byte, two rounds of four requests.
+__global__ __launch_bounds__(64) void k_tor_compare_bits(const Gt* fe, const Gt* x, int n, int32_t* codes,
+                                                         uint8_t* bits) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[4 * kFoldWords];
+  Team T = make_team(lds, kFoldWords);
+  fold_regs_init(T);
+  const int team = (threadIdx.x & 63) >> 4;
+  const int b = blockIdx.x;
+  XStream S = x_stream();
+  uint32_t m = 0;
+#pragma unroll 1
+  for (int j = 0; j < 2; j++) {
+    const int r = 8 * b + 4 * j + team;
+    const int ci = min(r, n - 1);
+    team_sync();
+    gt_load(T, S_A, fe + ci);
+    gt_load(T, S_B, x + ci, true);
+    fold_mul(T, S);  // A = fe conj(X)
+    team_sync();
+    gt_load(T, S_B, x + ci);
+    team_sync();
+    const bool eq = t12_equal(T, S_A, S_B);
+    bool mine = false;
+    if (T.tl == 0 && r < n) {
+      int32_t c = codes[r];
+      if (c == HG_OK) c = eq ? HG_OK : HG_ERR_SIG_INVALID;
+      codes[r] = c;
+      mine = c == HG_OK;
+    }
+    const uint64_t bal = __ballot(mine);
+#pragma unroll
+    for (int q = 0; q < 4; q++) m |= (uint32_t)((bal >> (16 * q)) & 1u) << (4 * j + q);
+  }
+  if (bits && threadIdx.x == 0) bits[b] = (uint8_t)m;
+}
+
 // ------------------------------------------------------------------ launchers
 void launch_gt_keys(const PointG2* reg, int n, const LineCoef* tab, const PointG1* h, Gt* out, hipStream_t s) {
   if (n > 0) k_gt_keys<4><<<nblk(n, 4), 64, 0, s>>>(reg, n, tab, h, out);
@@ -614,6 +938,7 @@ void launch_gt_blocks(const Gt* src, int stride, int nsrc, Gt* dst, int ndst, hi
 void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_t* codes, int nreg, int levels,
                     const Gt* win, const Gt* blk, const GtBlockIndex& bi, GtWork w, Gt* y, bool zero_hdr, hipStream_t s) {
   if (n <= 0) return;
+  if (w.torus && w.win_bits != 16) abort();  // a torus set has no 8-key fold table: never a classical read of it
   if (zero_hdr) (void)hipMemsetAsync(w.hdr, 0, sizeof(GtHdr), s);
   if (w.win_bits == 16)
     k_gt_plan<16><<<nblk(n, kPlanWaves), 64 * kPlanWaves, 0, s>>>(reqs, n, words, codes, nreg, levels, bi, w.plan,
@@ -621,8 +946,23 @@ void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_
   else
     k_gt_plan<8><<<nblk(n, kPlanWaves), 64 * kPlanWaves, 0, s>>>(reqs, n, words, codes, nreg, levels, bi, w.plan,
                                                                  w.hdr, w.terms, w.ord, w.cap, w.chunk, w.multi);
-  k_gt_chunks<<<w.chunk_grid, 64, 0, s>>>(win, blk, w.terms, w.ord, w.cap, w.plan, w.hdr, w.chunk, w.partial, y);
+  if (w.torus)
+    k_tor_chunks<<<w.chunk_grid, 64, 0, s>>>(win, blk, w.terms, w.ord, w.cap, w.plan, w.hdr, w.chunk, w.partial, y);
+  else
+    k_gt_chunks<<<w.chunk_grid, 64, 0, s>>>(win, blk, w.terms, w.ord, w.cap, w.plan, w.hdr, w.chunk, w.partial, y);
   k_gt_combine<<<n, 64, 0, s>>>(n, w.hdr, w.multi, w.plan, w.partial, y);
+}
+void launch_tor_scan(Gt* win, size_t nwin, Gt* blk, size_t nblk_, int nreg, int* flag, hipStream_t s) {
+  const size_t total = nwin + nblk_;
+  (void)hipMemsetAsync(flag, 0, sizeof(int), s);
+  if (total) k_tor_scan<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(TorTables{win, blk, nwin, nblk_, nreg}, flag);
+}
+void launch_tor_convert(Gt* win, size_t nwin, Gt* blk, size_t nblk_, int nreg, hipStream_t s) {
+  const size_t total = nwin + nblk_, per = 64 * kTorRun;
+  if (total) k_tor_convert<<<(unsigned)((total + per - 1) / per), 64, 0, s>>>(TorTables{win, blk, nwin, nblk_, nreg});
+}
+void launch_tor_compare(const Gt* fe, const Gt* x, int n, int32_t* codes, uint8_t* bits, hipStream_t s) {
+  if (n > 0) k_tor_compare_bits<<<(n + 7) / 8, 64, 0, s>>>(fe, x, n, codes, bits);
 }
 void launch_verify_sig(const PointG1* sigs, int n, const LineCoef* tab, const Gt* y, int32_t* codes, hipStream_t s) {
   if (n > 0) k_verify_sig<4, false><<<nblk(n, 4), 64, 0, s>>>(sigs, nullptr, 0, n, tab, y, nullptr, codes);

@@ -116,6 +116,33 @@ static size_t gt_table_bytes(const hg_ctx* c, int level) {
   return b;
 }
 
+// The level-2 fold tables (the 16-key windows and the blocks) to torus form,
+// in place, unless HG_GT_TORUS=0 or an entry has none: a registry may hold
+// keys whose sum over some window subset or block is zero (k and r - k), and
+// e(H, 0) = 1 has no torus form. The scan runs first and the host reads its
+// flag, so a set is converted whole or not at all. (The flag word is the
+// registry's membership counter, idle once resolve_subgroup has read it.)
+static bool gt_torus_enabled() {
+  static const bool on = env_int("HG_GT_TORUS", 1, 0, 1) != 0;
+  return on;
+}
+static int convert_torus_locked(hg_ctx* c, hipStream_t s, size_t nwin) {
+  c->cur.torus = false;
+  if (!gt_torus_enabled()) return HG_OK;
+  const size_t nblk = gt_block_count(c, nullptr);
+  HG_CHECK(c, c->sub_count.ensure(1));
+  int degenerate = 0;
+  launch_tor_scan(c->cur.gt_win.p, nwin, c->cur.gt_blk.p, nblk, (int)c->nreg, c->sub_count.p, s);
+  HG_CHECK(c, hipMemcpyAsync(&degenerate, c->sub_count.p, sizeof degenerate, hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, hipStreamSynchronize(s));
+  if (degenerate) return HG_OK;
+  launch_tor_convert(c->cur.gt_win.p, nwin, c->cur.gt_blk.p, nblk, (int)c->nreg, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  c->cur.torus = true;
+  return HG_OK;
+}
+
 // builds the tables up to `level` on stream s (inside a submission); kNoMem /
 // kOverBudget before any launch of the level that could not be held. The
 // budget covers both messages' tables.
@@ -150,6 +177,8 @@ static int build_gt_locked(hg_ctx* c, hipStream_t s, int level) {
     launch_gt_windows16(c->cur.gt_w8.p, nwin8, c->cur.gt_win.p, nwin16, s);
     int rc = check_launch(c);
     if (rc) return rc;
+    rc = convert_torus_locked(c, s, (size_t)nwin16 * 65536);
+    if (rc) return rc;
     c->cur.gt_level = 2;
   }
   return HG_OK;
@@ -161,6 +190,9 @@ static void gt_lower_cap(hg_ctx* c, int cap, bool oom) {
   if (cap < 0) cap = 0;
   if (cap < c->gt_cap) c->gt_cap = cap;
   if (oom && cap < c->oom_cap) c->oom_cap = cap;
+  // a torus set's block table is of no use without its 16-key windows: the
+  // lower level is rebuilt from the keys
+  if (c->gt_cap < 2 && c->cur.gt_level == 2 && c->cur.torus) c->cur.drop_tables();
   if (c->gt_cap < 2) c->cur.gt_win.reset();
   if (c->gt_cap < 1) c->cur.drop_tables();
   if (c->cur.gt_level > c->gt_cap) c->cur.gt_level = c->gt_cap;
@@ -340,6 +372,21 @@ static void gt_fold(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, int3
                  gw.win_bits == 16 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, zero_hdr,
                  s);
 }
+// the pairing in its stored form and the comparison with the fold's values:
+// how every flow ends on a table set in torus form, where gt_y holds X
+// (launch_tor_compare) and k_verify_sig's own comparison cannot be used
+static int pair_and_compare(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipStream_t s) {
+  const int n = (int)b.n;
+  PhaseTimer t(c, HG_PHASE_VERIFY, s);
+  const bool ran = launch_sig_form(form, b.sigs, c->flavor, n, c->d_lines.p, ws.sig_lines.p, ws.gt_fe.p, s);
+  t.stop();
+  if (!ran) {
+    c->err = "aggregate batch too large for its pairing form";
+    return HG_ERR_ARG;
+  }
+  launch_tor_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
+  return HG_OK;
+}
 
 // GT path, verdicts only, the fold beside the pairing:
 // s:    pairing (decodes its signatures) ............ -> wait -> compare
@@ -361,19 +408,21 @@ static int flow_gt_beside(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, co
   fold.stop();
   HG_CHECK(c, hipEventRecord(ws.ev_join, ws.side));
   HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
-  if (b.bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
+  if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
+  else if (b.bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
   else launch_gt_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, s);
   return HG_OK;
 }
 
 // GT path, verdicts only, in sequence: level check, signature decode and the
 // fold's counters in one launch, then the fold and k_verify_sig on the codes
-static int flow_gt_sequence(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
+static int flow_gt_sequence(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, const GtWork& gw, hipStream_t s) {
   const int n = (int)b.n;
   gt_prologue(c, b, ws, gw, s);
   PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
   gt_fold(c, b, ws, gw, b.codes, false, s);
   fold.stop();
+  if (gw.torus) return pair_and_compare(c, b, ws, form, s);
   PhaseTimer t(c, HG_PHASE_VERIFY, s);
   launch_verify_sig(ws.pts1.p, n, c->d_lines.p, ws.gt_y.p, b.codes, s);
   t.stop();
@@ -384,7 +433,7 @@ static int flow_gt_sequence(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& 
 // The G2 fold (g2_fold: no tables, or the caller wants the aggregate keys'
 // marshals), the GT fold beside it when use_gt, and (verify) the check:
 // k_verify_sig against the GT fold's values, or config 2 on the G2 fold's
-static int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, bool use_gt, bool g2_fold,
+static int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, bool use_gt, bool g2_fold, SigForm form,
                             const GtWork& gw, hipStream_t s) {
   const int n = (int)b.n;
   int32_t* d_lvl = b.lvl;
@@ -405,7 +454,9 @@ static int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, b
   if (verify) {
     launch_decode_g1(b.sigs, n, c->flavor, ws.pts1.p, ws.codes_b.p, s);
     k_agg_codes<<<nb(b.n), 256, 0, s>>>(ws.codes_b.p, d_lvl, c->cur.hash_eof ? 1 : 0, n, b.codes);
-    if (use_gt) {
+    if (use_gt && gw.torus) {
+      return pair_and_compare(c, b, ws, form, s);  // the verdict bitset with it
+    } else if (use_gt) {
       PhaseTimer t(c, HG_PHASE_VERIFY, s);
       launch_verify_sig(ws.pts1.p, n, c->d_lines.p, ws.gt_y.p, b.codes, s);
       t.stop();
@@ -441,20 +492,23 @@ static int aggregate_device_locked(hg_ctx* c, const AggBatch& b, bool verify, hi
     int rc = gt_acquire(c, ws, s, n, b.caps ? *b.caps : fold_caps_worst(c, n), level, gw, !is_lane);
     if (rc) return rc;
   }
+  // a set in torus form has one fold table, the 16-key windows
+  if (level > 0 && c->cur.gt_level == 2 && c->cur.torus) level = 2;
   gw.win_bits = level == 2 ? 16 : 8;
+  gw.torus = level == 2 && c->cur.torus;
   const bool use_gt = level > 0;
   const bool g2_fold = !use_gt || b.agg;
   const bool beside = use_gt && !g2_fold && pol.overlap;
   // the pairing's form: chosen once, it sizes the workspace and is what runs
   const SigForm form = sig_form(sig_env(), pol, n);
   const unsigned parts = (g2_fold ? kWsG2Fold : 0) | (b.agg ? kWsAggOut : 0) | (b.lvl ? 0 : kWsLevel) |
-                         (verify ? kWsVerify : 0) | (beside ? kWsPairing | kWsSide : 0);
+                         (verify ? kWsVerify : 0) | (beside ? kWsPairing | kWsSide : 0) | (gw.torus ? kWsPairing : 0);
   HG_CHECK(c, ws_ensure(ws, n, parts, {}, sig_form_ws_bytes(form, (int)n)));
   PhaseTimer all(c, HG_PHASE_SUBMIT, s);
   int rc;
   if (beside) rc = flow_gt_beside(c, b, ws, form, gw, s);
-  else if (use_gt && !g2_fold) rc = flow_gt_sequence(c, b, ws, gw, s);
-  else rc = flow_g2_or_mixed(c, b, ws, verify, use_gt, g2_fold, gw, s);
+  else if (use_gt && !g2_fold) rc = flow_gt_sequence(c, b, ws, form, gw, s);
+  else rc = flow_g2_or_mixed(c, b, ws, verify, use_gt, g2_fold, form, gw, s);
   if (rc) return rc;
   all.stop();
   rc = check_launch(c);
@@ -596,6 +650,12 @@ int hg_aggregate_tables(hg_ctx* c) {
   if (!c) return 0;
   std::lock_guard<std::mutex> g(c->mu);
   return c->cur.gt_level;
+}
+
+int hg_aggregate_tables_torus(hg_ctx* c) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> g(c->mu);
+  return c->cur.gt_level == 2 && c->cur.torus ? 1 : 0;
 }
 
 int hg_verify_aggregate_device(hg_ctx* c, const hg_request* d_reqs, size_t n, const uint64_t* d_words,

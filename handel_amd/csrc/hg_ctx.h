@@ -75,6 +75,11 @@ struct TableSet {
   // blocks; 2: + 16-key windows. Reset by a message or registry change;
   // raised by hg_prepare_aggregate or by request volume (gt_requests).
   int gt_level = 0;
+  // the form of gt_win and gt_blk, meaningful at gt_level 2 (set by every
+  // level-2 build): torus form (bn256_gt.hip), which only k_tor_chunks reads,
+  // so a torus set folds over its 16-key windows whatever level a submission
+  // asks for; false: Fp12 (the conversion is off, or an entry has no torus form)
+  bool torus = false;
   size_t gt_requests = 0;
   size_t table_bytes() const { return gt_key.bytes() + gt_w8.bytes() + gt_win.bytes() + gt_blk.bytes(); }
   // frees the tables (the hash stays); false if the set held none
@@ -85,6 +90,7 @@ struct TableSet {
     gt_win.reset();
     gt_blk.reset();
     gt_level = 0;
+    torus = false;
     return true;
   }
 };

@@ -142,6 +142,12 @@ class Engine:
         fold, 1 = GT fold over 8-key windows, 2 = over 16-key windows."""
         return int(self.L.hg_aggregate_tables(self.ctx))
 
+    def aggregate_tables_torus(self) -> bool:
+        """Whether the level-2 tables are kept in torus form
+        (hg_aggregate_tables_torus); False for a registry with a window subset
+        or block of keys that sums to zero, which has no such form."""
+        return bool(self.L.hg_aggregate_tables_torus(self.ctx))
+
     def registry_load(self, pks: bytes) -> np.ndarray:
         a = _u8(pks)
         n = len(a) // 128

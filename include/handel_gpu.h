@@ -182,6 +182,12 @@ int hg_prepare_aggregate_msg(hg_ctx* ctx, const uint8_t* msg, size_t len);
  * A go-flavor registry holding a key outside G2 stays at 0 (see
  * hg_registry_non_g2). */
 int hg_aggregate_tables(hg_ctx* ctx);
+/* 1 when the level-2 tables are kept in torus form (the fold then takes two
+ * Fp6 products per term instead of an Fp12 product; same verdicts), else 0:
+ * below level 2, with HG_GT_TORUS=0 in the environment, or for a registry in
+ * which some window subset or aligned block of keys sums to zero (such a
+ * value has no torus form; the tables then stay as they were). */
+int hg_aggregate_tables_torus(hg_ctx* ctx);
 /* Pins the table level of this context's aggregate submissions (0..2, capped
  * as above) or, with -1, returns them to the volume policy. New contexts take
  * HG_GT_LEVEL / HG_AGG_PATH=g2 (= 0) from the environment, else -1. */

@@ -491,6 +491,43 @@ def prog_line_n(lb, lc):
     return [lanes]
 
 
+def prog_tor_mul():
+    """dst = A * (alpha + w) for A = n + d w (n = the even powers of w, d the odd
+    ones: Fp6 = Fp2[v]/(v^3 - xi), v = w^2) and alpha in Fp6 in elements 0..5 of
+    slot B (B0, B1, B2):
+        n' = n alpha + v d,    d' = d alpha + n.
+    A unitary g = a + b w equals (alpha + w)/(alpha - w) with alpha = (1 + a)/b,
+    so a GT table entry kept as alpha multiplies a running X (value X/conj(X))
+    with two Fp6 products: 6 Fp products per lane instead of MUL12's 12. xi and
+    the sign of the i * i products are applied on the alpha side (9 pre-pass
+    values shared by all lanes); v d and n are the round's linear terms."""
+    lanes = []
+    for k in range(6):
+        m, odd = k // 2, k % 2
+        for c in "xy":
+            slots = []
+            for i in range(3):
+                j = (m - i) % 3
+                src = f"A{2 * i + odd}"
+                fx, fy = [(comp(src, "x"), 1)], [(comp(src, "y"), 1)]
+                ax, ay = [(comp(f"B{j}", "x"), 1)], [(comp(f"B{j}", "y"), 1)]
+                if m - i < 0:
+                    ax, ay = xi_lc(ax, ay)   # xi * alpha_j
+                if c == "x":
+                    slots += [(fx, ay), (fy, ax)]
+                else:
+                    slots += [(fy, ay), (fx, neg(ax))]
+            if odd:       # + n_m
+                lx, ly = [(comp(f"A{2 * m}", "x"), 1)], [(comp(f"A{2 * m}", "y"), 1)]
+            elif m > 0:   # + (v d)_m = d_{m-1}
+                lx, ly = [(comp(f"A{2 * m - 1}", "x"), 1)], [(comp(f"A{2 * m - 1}", "y"), 1)]
+            else:         # + (v d)_0 = xi d_2
+                lx, ly = xi_lc([(comp("A5", "x"), 1)], [(comp("A5", "y"), 1)])
+            slots.append((lx if c == "x" else ly, one()))
+            lanes.append(Lane(comp(f"D{k}", c), slots))
+    return [lanes]
+
+
 PROGRAMS = {
     "CYC_SQR": prog_cyc_sqr(),
     "SQR12": prog_sqr12(),
@@ -522,6 +559,9 @@ PROGRAMS["SQR12_12"] = prog_sqr12()
 PROGRAMS["LINE_FIX_12"] = prog_line_n("FB", "FC")
 PROGRAMS["MUL12_12"] = prog_mul12()
 PROGRAMS["CYC_SQR_X_12"] = prog_cyc_sqr_x_shared()  # r06: 24 pre-pass values (two per lane)
+# k_tor_chunks (bn256_gt.hip): a running product times a table entry in torus
+# form, in the GT-fold team layout (context FOLD), 12-lane teams
+PROGRAMS["TORMULF"] = prog_tor_mul()
 
 
 # ------------------------------------------------------------------ source-program interpreter
@@ -916,7 +956,7 @@ def run_xround(xr, F, A, B, limbs=False):
 X_FETCH_WORDS = 16  # words per lane one table prefetch brings in (>= the widest round)
 # programs whose pre-pass values live on lanes 0..11 only, so that they also
 # run in 12-lane teams (five per wave: k_gt_chunks, make_team12)
-PRE_LANES = {"MUL12F": 12, "SQR12_12": 12, "LINE_FIX_12": 12, "MUL12_12": 12, "CYC_SQR_X_12": 12}
+PRE_LANES = {"MUL12F": 12, "SQR12_12": 12, "LINE_FIX_12": 12, "MUL12_12": 12, "CYC_SQR_X_12": 12, "TORMULF": 12}
 KARATSUBA_MIN = 4   # jobs of this many products use Karatsuba (when check_xround allows)
 # Per-program thresholds. The default counts instructions: a Karatsuba product
 # saves 25 mads for 10 limb additions, and the job's column combination (~55
@@ -927,7 +967,9 @@ KARATSUBA_MIN = 4   # jobs of this many products use Karatsuba (when check_xroun
 # 3 rests on the interleaved A/B alone (profiles/r07ks_levers_ab.json,
 # r07ks_ab.json), not on a cycle price of the two instruction classes, which
 # nobody has measured in these kernels.
-KARATSUBA_MIN_PROG = {"CYC_SQR_X_12": 3}
+# TORMULF: the fold's mixed product, six products per lane: as for MUL12F the
+# instruction count decides (Karatsuba from four products on).
+KARATSUBA_MIN_PROG = {"CYC_SQR_X_12": 3, "TORMULF": 4}
 # FE: the register file from register 2 on; ML: slots C..J during the Miller loop
 # FOLD: the GT fold kernels' compact team region (bn256_gt.hip): slots F, A, B,
 # then registers ZERO and ONE, then the pre-pass scratch
@@ -941,6 +983,7 @@ X_PROGRAMS = {  # name -> (program, scratch context)
     "SQR12": "ML", "LINE_PK": "ML", "LINE_FIX": "ML", "CYC_SQR": "FE", "MUL12": "FE", "CYC_SQR_X": "FE",
     "FEVAL": "ML", "SDBL": "ML", "LFEV": "ML", "MUL12F": "FOLD",
     "SQR12_12": "ML", "LINE_FIX_12": "ML", "MUL12_12": "FE", "CYC_SQR_X_12": "FE",
+    "TORMULF": "FOLD",
 }
 
 
@@ -1115,6 +1158,12 @@ def validate_x(seed=2):
         assert unflat(run_xprogram(X["CYC_SQR_X"], dict(F), flat(cyc))) == O.f12_sqr(cyc), "xCYC_SQR_X"
         assert unflat(run_xprogram(X["MUL12"], dict(F), flat(f), flat(g))) == O.f12_mul(f, g), "xMUL12"
         assert unflat(run_xprogram(X["MUL12F"], dict(F), flat(f), flat(g))) == O.f12_mul(f, g), "xMUL12F"
+        # the fold's mixed product: X * (alpha + w), alpha in elements 0..5 of
+        # slot B (the other six are never read)
+        al = [(rng.randrange(P), rng.randrange(P)) for _ in range(3)]
+        aw = [al[0], (0, 1), al[1], (0, 0), al[2], (0, 0)]
+        junk = [rng.randrange(P) for _ in range(6)]
+        assert unflat(run_xprogram(X["TORMULF"], dict(F), flat(f), flat(al) + junk)) == O.f12_mul(f, aw), "xTORMULF"
         # the 12-lane (pre-pass on lanes 0..11) forms of k_verify_sig12
         assert unflat(run_xprogram(X["SQR12_12"], dict(F), flat(f))) == O.f12_sqr(f), "xSQR12_12"
         assert unflat(run_xprogram(X["CYC_SQR_X_12"], dict(F), flat(cyc))) == O.f12_sqr(cyc), "xCYC_SQR_X_12"
@@ -1240,8 +1289,12 @@ V_F_BASE = 12 + V_SCRATCH
 V_INSTANCES = ([("MDBL_1", ("F", "F")), ("MDBL_2", ("F", "F")), ("PDBL_1", ()), ("LINE_PK", ("F", "F"))]
                + [(f"PADD_{v}_{i}", ()) for v in ("POS", "NEG", "F1", "F2") for i in (1, 3)]
                + [(f"MADD_{v}_2", ("F", "F")) for v in ("POS", "NEG", "F1", "F2")])
+# bn256_gt.hip k_tor_chunks: X = X * (alpha + w), in the FOLD region. Listed
+# last, so the tables of every other instance keep their places in kXTab.
+TOR_INSTANCES = [("TORMULF", ("A", "A", "B"))]
 ALL_INSTANCES = ([(n, b, "") for n, b in INSTANCES] + [(n, b, "S") for n, b in SIG_INSTANCES]
-                 + [(n, b, "T") for n, b in SIG_T_INSTANCES] + [(n, b, "V") for n, b in V_INSTANCES])
+                 + [(n, b, "T") for n, b in SIG_T_INSTANCES] + [(n, b, "V") for n, b in V_INSTANCES]
+                 + [(n, b, "") for n, b in TOR_INSTANCES])
 
 
 
@@ -1532,6 +1585,7 @@ SIG_PROGRAMS = ("SDBL", "LFEV", "FEVAL", "LINE_FIX", "MUL12", "CYC_SQR_X", "CYC_
 REDC_FUSE_OFF = ("SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12")
 REDC_FUSE = {name: (ctx == "FE" or name in SIG_PROGRAMS) and name not in REDC_FUSE_OFF
              for name, ctx in X_PROGRAMS.items()}
+REDC_FUSE["TORMULF"] = False  # the fold's: several waves per SIMD, as MUL12F
 
 
 def touched(bx):

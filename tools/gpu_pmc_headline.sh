@@ -8,7 +8,7 @@ OUT=gpurun_out/pmc_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
 H="bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra"
-K="k_verify_sig|k_sig_|k_sig12|k_gt_|k_agg_"
+K="k_verify_sig|k_sig_|k_sig12|k_gt_|k_tor_|k_agg_"
 timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$K" -d $OUT/fetch -o run -- python3 $H > $OUT/fetch.log 2>&1 &&
 timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$K" -d $OUT/write -o run -- python3 $H > $OUT/write.log 2>&1 &&
 timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY --kernel-include-regex "$K" -d $OUT/sq -o run -- python3 $H > $OUT/sq.log 2>&1 &&
