@@ -78,6 +78,11 @@ void launch_extract_pk(const CheckIn* in, int n, PointG2* out, hipStream_t s);
 int diag_read(uint64_t* out, size_t n);
 void launch_g2_combine(const PointG2* a, const PointG2* b, int n, PointG2* out, hipStream_t s);
 void launch_fp12_op(int op, const uint8_t* a, const uint8_t* b, int n, uint8_t* out, hipStream_t s);
+// the instance probe (bn256_xprobe.hip): instances of the generator's ALL_INSTANCES, the team
+// region of one in a form (0: no such instance or form), one run of it on n raw regions
+int xprobe_instances();
+int xprobe_region_elems(int inst, int form);
+void launch_xprobe(int inst, int form, const uint32_t* in, int n, uint32_t* out, hipStream_t s);
 void launch_fp_mul(const uint32_t* a, const uint32_t* b, int n, uint32_t* out, hipStream_t s);
 
 }  // namespace hg

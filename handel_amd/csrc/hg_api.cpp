@@ -505,6 +505,31 @@ int hg_debug_fp12(hg_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t 
   return HG_OK;
 }
 
+// One bound team-program instance on n raw team regions (bn256_xprobe.hip)
+int hg_debug_xinst(hg_ctx* c, int inst, int form, const uint32_t* in, size_t n, uint32_t* out, int* region_elems) {
+  if (!c) return HG_ERR_ARG;
+  const int elems = xprobe_region_elems(inst, form);
+  if (elems == 0) return HG_ERR_ARG;  // no such instance, no such form, or not a form of its layout
+  if ((n && (!in || !out)) || n > (size_t)1 << 20) return HG_ERR_ARG;
+  if (region_elems) *region_elems = elems;
+  if (n == 0) return HG_OK;
+  const size_t bytes = n * (size_t)elems * 40;
+  std::lock_guard<std::mutex> g(c->mu);
+  HG_CHECK(c, hipSetDevice(c->device));
+  HG_CHECK(c, c->bytes_a.ensure(2 * bytes));
+  uint8_t* d = c->bytes_a.p;
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, c->stream));
+  launch_xprobe(inst, form, (const uint32_t*)d, (int)n, (uint32_t*)(d + bytes), c->stream);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(out, d + bytes, bytes, hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+
 // kernel: a SigForm by its number (bn256_sigform.h), whatever sig_form() would choose
 int hg_sig_pairing_device(hg_ctx* c, const uint8_t* d_sigs, size_t n, uint8_t* d_fe, int kernel, void* stream) {
   if (!c || (n && (!d_sigs || !d_fe)) || n > (size_t)INT32_MAX || kernel < 0 || kernel > 4) return HG_ERR_ARG;

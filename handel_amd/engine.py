@@ -352,6 +352,26 @@ class Engine:
         self._check(self.L.hg_debug_fp12(self.ctx, op, _ptr(x), _ptr(y), n, _ptr(out)), "hg_debug_fp12")
         return out.tobytes()
 
+    def xinst_region_elems(self, inst: int, form: int = 0) -> int:
+        """Elements of the team region of instance `inst` in `form` (hg_debug_xinst with n = 0)."""
+        e = ctypes.c_int()
+        self._check(self.L.hg_debug_xinst(self.ctx, int(inst), int(form), None, 0, None, ctypes.byref(e)),
+                    "hg_debug_xinst")
+        return e.value
+
+    def xinst(self, inst: int, regions: np.ndarray, form: int = 0) -> np.ndarray:
+        """One bound team-program instance on raw team regions (hg_debug_xinst):
+        regions and the result are uint32 arrays (n, region_elems, 10)."""
+        r = np.ascontiguousarray(regions, dtype=np.uint32)
+        elems = self.xinst_region_elems(inst, form)
+        if r.ndim != 3 or r.shape[1:] != (elems, 10):
+            raise ValueError(f"regions of shape {r.shape}, want (n, {elems}, 10)")
+        out = np.zeros_like(r)
+        n = r.shape[0]
+        self._check(self.L.hg_debug_xinst(self.ctx, int(inst), int(form), _ptr(r) if n else None, n,
+                                          _ptr(out) if n else None, None), "hg_debug_xinst")
+        return out
+
     def fp_mul(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.uint32)
         b = np.ascontiguousarray(b, dtype=np.uint32)

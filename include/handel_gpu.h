@@ -278,6 +278,19 @@ int hg_timing_read_phase(hg_ctx* ctx, int phase, double* total_ms, int* launches
  * Any other op: HG_ERR_ARG. */
 int hg_debug_fp12(hg_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
 
+/* Probe of ONE generated team-program instance (bn256_xtab.h), for the
+ * limb-for-limb comparison with the generator's model: inst is the
+ * instance's position in tools/gen_g2_schedule.py's ALL_INSTANCES. in and out
+ * hold n team regions of *region_elems elements of ten 32-bit limbs each,
+ * taken and returned as they are (no Montgomery conversion, no reduction, no
+ * marshal order): a region is copied into the team's LDS, the instance runs
+ * once on the team of the production kernel of its layout, and the whole
+ * region comes back. form 0: one-wave teams; form 1: the 2-wave split teams,
+ * layout-S instances only. An inst out of range, another form, or form 1 on
+ * another layout: HG_ERR_ARG, nothing runs, out and region_elems untouched.
+ * n = 0 only reports region_elems (may be NULL otherwise). n <= 2^20. */
+int hg_debug_xinst(hg_ctx* ctx, int inst, int form, const uint32_t* in, size_t n, uint32_t* out, int* region_elems);
+
 /* Kernel probe of the GT path's signature side (bench.py per-kernel
  * roofline, the GPU suite's cross-kernel check): d_fe[r] (480 bytes, the
  * engine's internal GT layout) = FE(Miller(G2Base at -sig_r)) for the n

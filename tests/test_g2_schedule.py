@@ -32,6 +32,11 @@ def test_committed_headers_are_current(tmp_path):
     with open(os.path.join(CSRC, "bn256_regs.h")) as f:
         assert f.read() == out.read_text()
     outx = tmp_path / "xtab.h"
-    G.emit_x(G.compile_all(), str(outx))
+    X = G.compile_all()
+    G.emit_x(X, str(outx))
     with open(os.path.join(CSRC, "bn256_xtab.h")) as f:
         assert f.read() == outx.read_text()
+    outp = tmp_path / "xprobe.h"
+    G.emit_xprobe(X, str(outp))
+    with open(os.path.join(CSRC, "bn256_xprobe.h")) as f:
+        assert f.read() == outp.read_text()

@@ -1600,7 +1600,9 @@ def touched(bx):
     return m
 
 
-def emit_x(X, path):
+def region_ends(X):
+    """Last element + 1 that the kernels' compact team regions must hold:
+    (layout S, layout T, FOLD context), before rounding up to an even count."""
     sig_end = SIG_F_BASE + REG["FC.y"] + 1  # team_miller_sig's registers: ZERO .. FC
     sig_t_end = SIG_T_F_BASE + REG["FC.y"] + 1  # team_miller_sig12's: ZERO, ONE, FB, FC
     fold_end = FOLD_F_BASE + 2               # ZERO, ONE
@@ -1614,6 +1616,11 @@ def emit_x(X, path):
                 sig_t_end = max(sig_t_end, t)
             if ctx == "FOLD":
                 fold_end = max(fold_end, t)
+    return sig_end, sig_t_end, fold_end
+
+
+def emit_x(X, path):
+    sig_end, sig_t_end, fold_end = region_ends(X)
     sig_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "S"}, key=list(X_PROGRAMS).index)
     sig_t_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "T"}, key=list(X_PROGRAMS).index)
     v_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "V"}, key=list(X_PROGRAMS).index)
@@ -1679,6 +1686,96 @@ def emit_x(X, path):
     return len(words)
 
 
+# ------------------------------------------------------------------ the instance probe (bn256_xprobe.h)
+# hg_debug_xinst runs ONE bound instance on a raw team region (bn256_xprobe.hip):
+# the dispatch from an instance's position in ALL_INSTANCES to its
+# XInst<...>::run is generated here. A probe layout is the team region a
+# production kernel gives the instance: D (the full region, kTeamWords), S, T,
+# V (the compact layouts) and F (the FOLD context's region).
+PROBE_LAYOUTS = ("D", "S", "T", "V", "F")
+# instances per probe kernel: a kernel inlines every instance of its group, and
+# the compiler's time per kernel grows faster than its size
+PROBE_GROUP_MAX = 12
+
+
+def probe_layout(name, layout):
+    return "F" if X_PROGRAMS[name] == "FOLD" else (layout or "D")
+
+
+def probe_region_elems(X):
+    """Elements of the team region per probe layout, as the kernels size it
+    (kTeamWords / 10, kSigTeamElems, kSigTTeamElems, kVTeamElems, kFoldTeamElems)."""
+    sig_end, sig_t_end, fold_end = region_ends(X)
+    v_end = V_F_BASE + NREGS
+    return {"D": F_BASE + NREGS, "S": sig_end + sig_end % 2, "T": sig_t_end + sig_t_end % 2,
+            "V": v_end + v_end % 2, "F": fold_end + fold_end % 2}
+
+
+def probe_reg_base(name, layout):
+    """Team element of register 0 (ZERO; ONE follows) in the instance's region."""
+    return {"S": SIG_F_BASE, "T": SIG_T_F_BASE, "V": V_F_BASE}.get(layout, F_BASE_CTX[X_PROGRAMS[name]])
+
+
+def instance_rounds(X, i):
+    """The bound rounds of instance i of ALL_INSTANCES (run_bound / run_bound_limbs run them)."""
+    name, binding, layout = ALL_INSTANCES[i]
+    return [bind(xr, binding, X_PROGRAMS[name], layout) for xr in X[name]]
+
+
+def probe_groups():
+    """[(probe layout, [instance numbers])]: each layout's instances in chunks
+    of PROBE_GROUP_MAX, one probe kernel per chunk."""
+    groups = []
+    for lay in PROBE_LAYOUTS:
+        idx = [i for i, (n, _, l) in enumerate(ALL_INSTANCES) if probe_layout(n, l) == lay]
+        groups += [(lay, idx[k:k + PROBE_GROUP_MAX]) for k in range(0, len(idx), PROBE_GROUP_MAX)]
+    return groups
+
+
+def emit_xprobe(X, path):
+    elems = probe_region_elems(X)
+    groups = probe_groups()
+    group_of = {i: g for g, (_, idx) in enumerate(groups) for i in idx}
+    assert sorted(group_of) == list(range(len(ALL_INSTANCES)))
+    lines = ["// Generated by tools/gen_g2_schedule.py — do not edit.",
+             "// The instance probe's dispatch (bn256_xprobe_kernel.h, hg_debug_xinst): instance i",
+             "// is entry i of the generator's ALL_INSTANCES. kXProbeInfo gives its team",
+             "// region (a probe layout and its element count) and the probe kernel (group)",
+             "// that holds it; XProbeGroup<G>::run is that kernel's switch over its instances,",
+             "// each case the call XInst<...>::run of the instance's call sites.",
+             "#pragma once", "namespace hg {",
+             "enum XProbeLayout { " + ", ".join(f"XPL_{l}" for l in PROBE_LAYOUTS)
+             + " };  // full region, layouts S, T, V, FOLD context",
+             "struct XProbeInfo { unsigned char layout, group; unsigned short elems; };",
+             f"static constexpr int kXProbeInstances = {len(ALL_INSTANCES)};",
+             f"static constexpr int kXProbeGroups = {len(groups)};",
+             f"static constexpr XProbeInfo kXProbeInfo[kXProbeInstances] = {{"]
+    for i, (name, binding, layout) in enumerate(ALL_INSTANCES):
+        lay = probe_layout(name, layout)
+        lines.append(f"  {{XPL_{lay}, {group_of[i]}, {elems[lay]}}},  // {i}: {name}"
+                     f"{'_' + layout if layout else ''}<{', '.join(binding)}>")
+    lines.append("};")
+    lines.append("static constexpr int kXProbeGroupLayout[kXProbeGroups] = {"
+                 + ", ".join(f"XPL_{lay}" for lay, _ in groups) + "};")
+    lines.append("#define HG_XPROBE_GROUPS(X) " + " ".join(f"X({g})" for g in range(len(groups))))
+    lines.append("#define HG_XPROBE_S_GROUPS(X) " + " ".join(f"X({g})" for g, (lay, _) in enumerate(groups) if lay == "S"))
+    lines.append("template <int G> struct XProbeGroup;")
+    for g, (lay, idx) in enumerate(groups):
+        lines.append(f"template <> struct XProbeGroup<{g}> {{ HG_DEV static void run(int inst, const Team& T, XStream& S) {{")
+        lines.append("  switch (inst) {  // kernel-uniform")
+        for i in idx:
+            name, binding, layout = ALL_INSTANCES[i]
+            targs = f"XP_{name}{'_' + layout if layout else ''}" + "".join(f", S_{b}" for b in binding)
+            lines.append(f"    case {i}: XInst<{targs}>::run(T, S, xh_none()); break;")
+        lines.append("    default: break;")
+        lines.append("  }")
+        lines.append("} };")
+    lines.append("}  // namespace hg")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return len(groups)
+
+
 def emit_regs(path):
     """bn256_regs.h: the numbers of the team's register file (REG)."""
     lines = ["// Generated by tools/gen_g2_schedule.py — do not edit.",
@@ -1699,7 +1796,8 @@ if __name__ == "__main__":
     Xp = validate_x()
     check_instances(Xp)
     nwords = emit_x(Xp, os.path.join(csrc, "bn256_xtab.h"))
-    print(len(ALL_INSTANCES), "instances,", nwords * 4, "table bytes")
+    ngroups = emit_xprobe(Xp, os.path.join(csrc, "bn256_xprobe.h"))
+    print(len(ALL_INSTANCES), "instances,", nwords * 4, "table bytes,", ngroups, "probe kernels")
     for name, rounds in Xp.items():
         print(name, [(r.nv, r.nt, r.np, r.nl, r.words()) for r in rounds])
-    print("validated and wrote bn256_regs.h, bn256_xtab.h")
+    print("validated and wrote bn256_regs.h, bn256_xtab.h, bn256_xprobe.h")
