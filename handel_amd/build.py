@@ -19,10 +19,12 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT_DIR, "libhandel_gpu.so")
 DIAG_LIB = os.path.join(OUT_DIR, "libhandel_gpu_diag.so")
-SOURCES = ["bn256_verify.hip", "bn256_pair.hip", "bn256_kernels.hip", "bn256_gt.hip", "bn256_sig12.hip", "bn256_sigw2.hip", "bn256_xprobe.hip", "bn256_xprobew2.hip", "hg_api.cpp", "hg_aggregate.cpp", "hg_intake.cpp",
-           "hg_batcher.cpp", "hg_packets.hip", "hg_service.cpp", "hg_stores.hip", "hg_merge.hip"]
-HEADERS = ["bn256_fp.h", "bn256_curve.h", "bn256_team.h", "bn256_kernels.h", "bn256_constants.h",
-           "bn256_regs.h", "bn256_pairing.h", "bn256_xprog.h", "bn256_xtab.h", "bn256_xprobe.h", "bn256_xprobe_kernel.h", "bn256_redq.h", "bn256_inv.h", "bn256_agg.h", "bn256_gt.h", "bn256_decode.h", "hg_packets.h", "hg_stores.h", "hg_shm.h", "hg_codes.h", "hg_dev.h", "hg_ctx.h", "hg_sha256.h", "bn256_sigfe.h", "bn256_sigteam.h", "bn256_sigsplit.h", "bn256_sigform.h"]
+SOURCES = ["bn256_verify.hip", "bn256_pair.hip", "bn256_kernels.hip", "bn256_gt.hip", "bn256_gttab.hip",
+           "bn256_sig16.hip", "bn256_sig12.hip", "bn256_sigw2.hip", "bn256_xprobe.hip", "bn256_xprobew2.hip", "hg_api.cpp",
+           "hg_aggregate.cpp", "hg_intake.cpp", "hg_batcher.cpp", "hg_packets.hip", "hg_service.cpp", "hg_stores.hip",
+           "hg_merge.hip"]
+# every header of csrc/: a change to any of them rebuilds the library
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 ARCH = os.environ.get("HG_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-unused-result"]

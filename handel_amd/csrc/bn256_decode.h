@@ -1,6 +1,6 @@
 // bn256_decode.h — signature decode shared by the decode kernels
-// (bn256_kernels.hip) and the pairing kernel of the GT path (bn256_gt.hip),
-// which decodes its own signature so the prologue can run off its critical path.
+// (bn256_kernels.hip) and the GT path's pairing kernels (bn256_sig16.hip and its
+// siblings), which decode their own signatures, off the prologue's critical path.
 #pragma once
 #include "bn256_curve.h"
 #include "bn256_kernels.h"

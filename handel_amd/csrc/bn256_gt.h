@@ -1,7 +1,6 @@
-// bn256_gt.h — data of the GT aggregate-verification path (bn256_gt.hip).
+// bn256_gt.h — data of the GT path: tables (bn256_gttab.hip), fold and comparison (bn256_gt.hip).
 #pragma once
 #include "bn256_kernels.h"
-#include "bn256_sigform.h"
 
 namespace hg {
 
@@ -64,27 +63,9 @@ void launch_gt_blocks(const Gt* src, int stride, int nsrc, Gt* dst, int ndst, hi
 void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_t* codes, int nreg, int levels,
                     const Gt* win, const Gt* blk, const GtBlockIndex& bi, GtWork w, Gt* y, bool zero_hdr,
                     hipStream_t s);
-// FE(Miller(G2Base at -sig_r)) == y[r] for every request still HG_OK
-void launch_verify_sig(const PointG1* sigs, int n, const LineCoef* tab, const Gt* y, int32_t* codes, hipStream_t s);
-// the same check in two launches, so the fold can run beside the pairing:
-// fe[r] = FE(Miller(G2Base at -sig_r)) from the 64-byte marshals (decoded in
-// the kernel), then fe[r] == y[r] where still HG_OK (launch_gt_compare).
-// Which of the pairing's forms a batch runs, and why, is bn256_sigform.h's
-// sig_form(); these run it. sig_env: the A/B knobs, read once.
-// ws: sig_form_ws_bytes(f, n) bytes (bn256_sigform.h; none for most forms).
-// launch_sig_form: false, with nothing launched, for a 12-lane form above
-// kSig12MaxN (HG_ERR_ARG to the caller: the codes must not stay HG_OK).
-const SigEnv& sig_env();
-bool launch_sig_form(SigForm f, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws, Gt* fe,
-                     hipStream_t s);
-// the split chain's final exponentiation (k_sig12_norm, k_sig12_ninv,
-// k_sig12_fe) of n Miller values in fe, in place: config 2's second half
-// (launch_verify_split); ws: fe12_ws_bytes(n) bytes. false as launch_sig_form
-size_t fe12_ws_bytes(int n);
-bool launch_fe12(Gt* fe, int n, uint8_t* ws, hipStream_t s);
 // The torus form of the 16-key window table (nwin entries) and the block table
 // (nblk): each entry g = a + b w becomes alpha = (1 + a)/b in its first six
-// elements, zero in the rest (bn256_gt.hip). launch_tor_scan: *flag = 1 when an
+// elements, zero in the rest (bn256_gttab.hip). launch_tor_scan: *flag = 1 when an
 // entry has no alpha (b = 0), else 0; nothing is written. launch_tor_convert:
 // in place, only after a clean scan. A fold over converted tables (GtWork.torus)
 // leaves y[r] = X with e(H, aggregate key)'s conjugate = X/conj(X), which only

@@ -1,5 +1,7 @@
 // bn256_gt.hip — aggregate verification in GT (the default path of
-// hg_verify_aggregate and its device / multisig variants).
+// hg_verify_aggregate and its device / multisig variants): the per-batch fold
+// and comparison (FOLD team region: bn256_gtfold.h). Its tables:
+// bn256_gttab.hip; the pairing: bn256_sigpair.h.
 //
 // processing.go:342-368 verifies a multisignature as
 //     e(H, sum of the level's set keys) == e(sig, G2Base)
@@ -19,197 +21,15 @@
 //     (G2 doubling and addition programs, the pk lines) is gone.
 // The verdict is the reference's for every registry of keys in G2 (keys are
 // k * G2Base; the same parity scope as k_verify).
-//
-// Team layouts: k_gt_keys / k_verify_sig use the pairing team region of
-// k_verify (bn256_pairing.h); the fold kernels use the compact FOLD region of
-// the generator (slots F, A, B, registers ZERO and ONE, pre-pass scratch:
-// kFoldTeamElems elements: 9.6 KB per 4-team workgroup), so several fold
-// waves share a SIMD, also beside k_verify_sig's waves.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
 #include "bn256_agg.h"
-#include "bn256_decode.h"
 #include "bn256_gt.h"
-#include "bn256_pairing.h"
-#include "bn256_sigfe.h"
-#include "bn256_sigteam.h"
+#include "bn256_gtfold.h"
 
 namespace hg {
-static inline int nblk(int n, int b) { return (n + b - 1) / b; }
-
-static constexpr int kFoldWords = kFoldTeamElems * 10;
-static_assert(kFoldWords % 2 == 0, "8-byte aligned team regions");
-
-// the FOLD region's constant registers (ZERO for padded products, ONE)
-HG_DEV void fold_regs_init(const Team& T) {
-  if (T.tl == 0) {
-    Fp z, o;
-    fp_zero(z);
-    fp_one(o);
-    st_fp_a8(T.base + (kFoldRegBase + 0) * 10, z.l);
-    st_fp_a8(T.base + (kFoldRegBase + 1) * 10, o.l);
-  }
-  team_sync();
-}
-using IMulF = XInst<XP_MUL12F, S_A, S_A, S_B>;  // A = A * B in the FOLD region
-// (the hint re-fetches the same round's words: measured 1-2 % faster for the
-// fold than keeping them, which frees 10 VGPRs but not a wave per SIMD,
-// profiles/r05fb_fold_refetch_ab.json)
-HG_DEV void fold_mul(const Team& T, XStream& S) {
-  team_sync();
-  IMulF::run(T, S, xh<IMulF>());
-}
-
-// ------------------------------------------------------------------ per-(message, registry) tables
-// G_i = e(H, pk_i): the pairing team programs of k_verify with the G2Base
-// pairing switched off (unit lines), then the final exponentiation.
-template <int TEAMS>
-__global__ __launch_bounds__(64) void k_gt_keys(const PointG2* reg, int n, const LineCoef* tab, const PointG1* hpt,
-                                                Gt* out) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[TEAMS * kTeamWords];
-  Team T = make_team(lds, kTeamWords);
-  uint32_t* F = team_regs(T);
-  const int idx = blockIdx.x * TEAMS + (threadIdx.x >> 4);
-  const bool valid = idx < n;
-  const PointG2& Q = reg[valid ? idx : n - 1];
-  CheckCtx C;
-  C.qx = Q.x;
-  C.qy = Q.y;
-  C.hx = hpt->x;
-  C.hy = hpt->y;
-  C.sx = hpt->x;
-  C.sy = hpt->y;
-  C.use_q = Q.inf == 0;
-  C.use_s = false;
-  if (!C.use_q) {  // e(H, infinity) = 1: unit lines on a well-defined doubling chain
-    const Fp2 gx = HG_G2X, gy = HG_G2Y;
-    C.qx = gx;
-    C.qy = gy;
-  }
-  XStream S = x_stream();
-  team_miller_check(T, F, C, tab, false, S, final_exp_hint());
-  team_final_exp_fc(T, F, S);  // the GT tables: FE^m (team_final_exp_fc)
-  if (valid) gt_store(T, S_F, out + idx);
-}
-
-// Window subset products, first pass: for each window w and half h (keys
-// 8w + 4h .. 8w + 4h + 3) the 16 products of the half's subsets, by the
-// recurrence P(s) = P(s without its lowest bit) * G(lowest bit), kept in LDS;
-// entries s (h = 0) and s << 4 (h = 1) of the window's table. Absent keys
-// (past the registry) are 1.
-__global__ __launch_bounds__(64) void k_gt_nib(const Gt* key, int nreg, int nwin, Gt* win) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[4 * kFoldWords];
-  __shared__ __attribute__((aligned(16))) uint32_t dp[4][16 * kFp12Words];
-  Team T = make_team(lds, kFoldWords);
-  fold_regs_init(T);
-  const int team = (threadIdx.x & 63) >> 4;
-  const int task = blockIdx.x * 4 + team;
-  const bool valid = task < 2 * nwin;
-  const int w = valid ? task >> 1 : 0, h = task & 1;
-  uint32_t* D = dp[team];
-  XStream S = x_stream();
-  Fp one;
-  gt_one_value(one, T);
-  if (T.active) st_fp_a8(D + T.e * 10, one.l);  // P(empty) = 1
-#pragma unroll 1
-  for (int s = 1; s < 16; s++) {
-    const int lo = s & -s, rest = s ^ lo;
-    if (rest == 0) {
-      const int j = 31 - __clz(lo);
-      const int kidx = 8 * w + 4 * h + j;
-      gt_load_or_one(T, S_A, key + (kidx < nreg ? kidx : 0), kidx < nreg);
-    } else {
-      lds_fp12_copy(T, slot(T, S_A), D + rest * kFp12Words);
-      lds_fp12_copy(T, slot(T, S_B), D + lo * kFp12Words);
-      fold_mul(T, S);
-    }
-    team_sync();
-    lds_fp12_copy(T, D + s * kFp12Words, slot(T, S_A));
-  }
-  team_sync();
-  if (!valid) return;
-  Gt* tw = win + (size_t)w * 256;
-#pragma unroll 1
-  for (int s = (h ? 1 : 0); s < 16; s++) {
-    Fp v;
-    ld_fp_a8(v, D + s * kFp12Words + T.e * 10);
-    if (!T.active) continue;
-    uint2* dst = (uint2*)__builtin_assume_aligned(tw[h ? s << 4 : s].w + 10 * T.e, 8);
-#pragma unroll
-    for (int i = 0; i < 5; i++) dst[i] = make_uint2(v.l[2 * i], v.l[2 * i + 1]);
-  }
-}
-
-// Second pass: entry (hi << 4) | lo = entry(lo) * entry(hi << 4) for hi, lo
-// != 0; one team per (window, hi), 15 products.
-__global__ __launch_bounds__(64) void k_gt_cross(int nwin, Gt* win) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[4 * kFoldWords];
-  Team T = make_team(lds, kFoldWords);
-  fold_regs_init(T);
-  const int task = blockIdx.x * 4 + ((threadIdx.x & 63) >> 4);
-  const bool valid = task < 15 * nwin;
-  const int w = valid ? task / 15 : 0, hi = valid ? task % 15 + 1 : 1;
-  Gt* tw = win + (size_t)w * 256;
-  XStream S = x_stream();
-#pragma unroll 1
-  for (int lo = 1; lo < 16; lo++) {
-    gt_load(T, S_A, tw + lo);
-    gt_load(T, S_B, tw + (hi << 4));
-    fold_mul(T, S);
-    team_sync();
-    if (valid) gt_store(T, S_A, tw + ((hi << 4) | lo));
-  }
-}
-
-// 16-key windows: entry (hi << 8) | lo = w8[2w][lo] * w8[2w + 1][hi]; one
-// team per (window, hi), 256 products, the next left operand in flight.
-__global__ __launch_bounds__(64) void k_gt_win16(const Gt* w8, int nwin8, int nwin16, Gt* w16) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTeams12 * kFoldWords];
-  Team T = make_team12(lds, kFoldWords);  // five 12-lane teams per wave
-  fold_regs_init(T);
-  const int task = blockIdx.x * kTeams12 + team12_index();
-  const bool valid = task < 256 * nwin16;
-  const int w = valid ? task >> 8 : 0, hi = task & 255;
-  const Gt* lo_tab = w8 + (size_t)(2 * w) * 256;
-  const bool has_hi = 2 * w + 1 < nwin8;
-  Gt* dst = w16 + (size_t)w * 65536 + (size_t)hi * 256;
-  XStream S = x_stream();
-  Fp hv, one, nxt;
-  gt_one_value(one, T);
-  gt_read(hv, w8 + (size_t)(has_hi ? 2 * w + 1 : 2 * w) * 256 + hi, T);
-  fp_sel(hv, has_hi, hv, one);
-  gt_read(nxt, lo_tab, T);
-#pragma unroll 1
-  for (int lo = 0; lo < 256; lo++) {
-    gt_put(T, S_A, nxt, false);
-    gt_put(T, S_B, hv, false);
-    if (lo + 1 < 256) gt_read(nxt, lo_tab + lo + 1, T);
-    fold_mul(T, S);
-    team_sync();
-    if (valid) gt_store(T, S_A, dst + lo);
-  }
-}
-
-
-// Block products, one level: dst[j] = src[2j] * src[2j + 1] (the last block of
-// a level may be clipped: src[2j + 1] absent -> 1). src entries `stride` apart.
-__global__ __launch_bounds__(64) void k_gt_blocks(const Gt* src, int stride, int nsrc, Gt* dst, int ndst) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[4 * kFoldWords];
-  Team T = make_team(lds, kFoldWords);
-  fold_regs_init(T);
-  const int j = blockIdx.x * 4 + ((threadIdx.x & 63) >> 4);
-  const bool valid = j < ndst;
-  const int a = valid ? 2 * j : 0;
-  XStream S = x_stream();
-  gt_load(T, S_A, src + (size_t)a * stride);
-  gt_load_or_one(T, S_B, src + (size_t)(a + 1 < nsrc ? a + 1 : a) * stride, a + 1 < nsrc);
-  fold_mul(T, S);
-  team_sync();
-  if (valid) gt_store(T, S_A, dst + j);
-}
-
 // ------------------------------------------------------------------ the fold of a batch
 // Term encoding: bits 0..29 index a GT table, bit 30 = conjugate on load,
 // bit 31 = the block table (else the window table).
@@ -395,6 +215,48 @@ __global__ __launch_bounds__(64 * kPlanWaves) void k_gt_plan(const AggRequest* r
 // The next term is fetched from HBM into registers while the current product
 // runs.
 static_assert(kGtChunkTeams == kTeams12, "k_gt_chunks' teams per workgroup");
+// k_gt_plan's chunk schedule, as k_gt_chunks and k_tor_chunks both walk it:
+// entry k is a long chunk for k < nlong (ord from 0), a short tail after (ord
+// down from cap - 1); a team without a chunk (!valid) has cnt = 0.
+struct FoldChunk {
+  int first, cnt;  // the chunk's terms: terms[first .. first + cnt)
+  int r, c;        // its request, its place in the batch's chunk list (partial[c])
+  bool single;     // the request's only chunk: the product is y[r]
+};
+HG_DEV FoldChunk fold_chunk(bool valid, int k, int nlong, const int2* ord, int cap, const GtReq* plan, int chunk) {
+  FoldChunk ch = {0, 0, 0, 0, false};
+  if (valid) {
+    const int2 e = k < nlong ? ord[k] : ord[cap - 1 - (k - nlong)];
+    ch.c = e.x;
+    ch.r = e.y;
+    const GtReq g = plan[ch.r];
+    ch.first = g.term_off + (ch.c - g.chunk_off) * chunk;
+    ch.cnt = min(chunk, g.term_off + g.m - ch.first);
+    ch.single = g.chunks == 1;
+  }
+  return ch;
+}
+// the longest chunk of the wave's teams: every team runs that many rounds
+HG_DEV int wave_max(int v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v = max(v, __shfl_xor(v, d));
+  return v;
+}
+// The chunk's term words, read once: lane tl of the team holds term tl (terms
+// past 12 are read from the list), so no table read waits on a dependent index
+// load. term(i), 0 past the chunk's end: i wave-uniform, every lane shuffles.
+struct TermWindow {
+  const uint32_t* terms;  // the batch's term list (wave-uniform)
+  int first, cnt, lane0;  // the chunk's terms in it; the team's first lane in the wave
+  uint32_t mine;
+  HG_DEV TermWindow(const Team& T, int team, const uint32_t* terms_, const FoldChunk& ch)
+      : terms(terms_), first(ch.first), cnt(ch.cnt), lane0(12 * team),
+        mine(T.tl < ch.cnt ? terms_[ch.first + T.tl] : 0u) {}
+  HG_DEV uint32_t operator()(int i) const {
+    const uint32_t v = (uint32_t)__shfl((int)mine, lane0 + (i < 12 ? i : 0), 64);
+    return i < 12 ? v : (i < cnt ? terms[first + i] : 0u);
+  }
+};
 // minimum waves per SIMD the compiler sizes k_gt_chunks' registers for (A/B
 // builds: 3 -> 168 VGPRs with 37 spills, fold alone 0.59 -> 0.66 ms,
 // profiles/r05fa_fold_occupancy_ab.json; 1 = the compiler's choice, 200 VGPRs)
@@ -413,29 +275,9 @@ __global__ __launch_bounds__(64, HG_CHUNK_WAVES) void k_gt_chunks(const Gt* win,
   for (int base = blockIdx.x * kTeams12; base < total; base += gridDim.x * kTeams12) {  // wave-uniform
     const int k = base + team;
     const bool valid = k < total && T.active;
-    int first = 0, cnt = 0, r = 0, c = 0;
-    bool single = false;
-    if (valid) {
-      const int2 e = k < nlong ? ord[k] : ord[cap - 1 - (k - nlong)];
-      c = e.x;
-      r = e.y;
-      const GtReq g = plan[r];
-      first = g.term_off + (c - g.chunk_off) * chunk;
-      cnt = min(chunk, g.term_off + g.m - first);
-      single = g.chunks == 1;
-    }
-    int maxc = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) maxc = max(maxc, __shfl_xor(maxc, d));
-    // the chunk's term words, read once: lane tl of the team holds term tl
-    // (terms past 12 are read from the list), so no table read waits on a
-    // dependent index load
-    const uint32_t my_t = T.tl < cnt ? terms[first + T.tl] : 0u;
-    const int tbase = 12 * team;
-    auto term = [&](int i) -> uint32_t {  // wave-uniform i: every lane runs the shuffle
-      const uint32_t v = (uint32_t)__shfl((int)my_t, tbase + (i < 12 ? i : 0), 64);
-      return i < 12 ? v : (i < cnt ? terms[first + i] : 0u);
-    };
+    const FoldChunk ch = fold_chunk(valid, k, nlong, ord, cap, plan, chunk);
+    const int cnt = ch.cnt, maxc = wave_max(cnt);
+    const TermWindow term(T, team, terms, ch);
     Fp cur, n1, n2, one;
     gt_one_value(one, T);
     fp_zero(n1);
@@ -461,7 +303,7 @@ __global__ __launch_bounds__(64, HG_CHUNK_WAVES) void k_gt_chunks(const Gt* win,
       fold_mul(T, S);
     }
     team_sync();
-    if (valid) gt_store(T, S_A, single ? y + r : partial + c);
+    if (valid) gt_store(T, S_A, ch.single ? y + ch.r : partial + ch.c);
     team_sync();
   }
 }
@@ -505,48 +347,6 @@ __global__ __launch_bounds__(64) void k_gt_combine(int n, const GtHdr* hdr, cons
   }
   team_sync();
   if (team == 0) gt_store(T, S_A, y + r);
-}
-
-// kStore: the signature is decoded here from its marshal (sig_bytes, the
-// flavor's rules): the prologue that decodes it for the verdict codes runs on
-// the side stream, off this kernel's critical path. A signature that fails to
-// decode gives a meaningless FE value, which k_gt_compare never reads (its code
-// is the decode error already).
-// kPad: one pairing wave per SIMD (below); SigForm::W16 is the unpadded
-// variant, two waves per SIMD when two batches are in flight
-template <int TEAMS, bool kStore, bool kPad = (TEAMS == 4)>
-__global__ __launch_bounds__(64) void k_verify_sig(const PointG1* sigs, const uint8_t* sig_bytes, int flavor, int n,
-                                                   const LineCoef* tab, const Gt* y, Gt* fe, int32_t* codes) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[TEAMS * kSigTeamWords];
-  // kStore runs beside the GT fold on another stream, whose waves share the
-  // SIMDs: the pairing wave (the step's critical path) wins the issue
-  // arbitration, the fold's waves take the cycles it leaves
-  if (kStore) __builtin_amdgcn_s_setprio(3);
-  // one pairing wave per SIMD: the kernel needs 233 VGPRs, which would let a
-  // second batch's pairing waves (two contexts in flight) share SIMDs and
-  // crowd the fold's workgroups out of the CU's LDS; marking v255 and one
-  // AGPR used makes its allocation exceed half of the 512-entry file
-  if constexpr (kPad) asm volatile("" ::: "v255", "a0");
-  Team T = make_team(lds, kSigTeamWords);
-  uint32_t* F = T.base + kSigRegBase * 10;
-  const int idx = blockIdx.x * TEAMS + (threadIdx.x >> 4);
-  const bool valid = idx < n;
-  const int ci = valid ? idx : n - 1;
-  PointG1 sg;
-  if (kStore) (void)decode_g1_one(sig_bytes + (size_t)ci * 64, flavor, sg);
-  else sg = sigs[ci];
-  XStream S = x_stream();
-  team_miller_sig(T, F, sg.x, sg.y, sg.inf == 0, tab, S, SigFE<SigProgs16>::final_exp_hint_s());
-  SigFE<SigProgs16>::team_final_exp_fc_s(T, S);
-  if (kStore) {
-    team_sync();
-    if (valid) gt_store(T, S_F, fe + idx);
-    return;
-  }
-  gt_load(T, S_A, y + ci);
-  team_sync();
-  const bool ok = t12_equal(T, S_F, S_A);
-  if (valid && T.tl == 0 && codes[idx] == HG_OK) codes[idx] = ok ? HG_OK : HG_ERR_SIG_INVALID;
 }
 
 // fe[r] == y[r] (both canonical: word equality) for every request still HG_OK;
@@ -595,203 +395,14 @@ __global__ __launch_bounds__(64) void k_gt_compare_bits(const Gt* fe, const Gt* 
   if (l == 0) bits[b] = (uint8_t)(m & 0xffu);
 }
 
-// ------------------------------------------------------------------ torus form of the fold's tables
-// A table entry is unitary: g = a + b w with a, b in Fp6 = Fp2[v]/(v^3 - xi)
-// (v = w^2: a holds the even powers of w, b the odd ones) and g conj(g) = 1,
-// so g = (alpha + w)/(alpha - w) with alpha = (1 + a)/b. The 16-key window
-// table and the block table keep alpha in the first six elements of each
-// entry (the entry stride stays sizeof(Gt); the other six are zero). A running
-// product is any X in Fp12 with value X/conj(X): a term multiplies it by
-// (alpha + w), two Fp6 products (TORMULF) instead of an Fp12 product; the
-// conjugate of a term is -alpha; partial products combine by the plain Fp12
-// product (k_gt_combine, unchanged); and the check fe == X/conj(X) is
-// fe conj(X) == X (k_tor_compare_bits), so nothing is inverted per request.
-// g = +-1 (b = 0) has no alpha: k_tor_scan finds such entries before anything
-// is written, and a table set with one stays in Fp12 form (k_gt_chunks).
-struct Fp6 {
-  Fp2 c[3];  // c0 + c1 v + c2 v^2
-};
-HG_DEV void f6_mul(Fp6& r, const Fp6& a, const Fp6& b) {
-  Fp2 t0, t1, t2, s, u, w;
-  Fp6 o;
-  f2_mul(t0, a.c[0], b.c[0]);
-  f2_mul(t1, a.c[1], b.c[1]);
-  f2_mul(t2, a.c[2], b.c[2]);
-  f2_add(s, a.c[1], a.c[2]);
-  f2_add(u, b.c[1], b.c[2]);
-  f2_mul(w, s, u);
-  f2_sub(w, w, t1);
-  f2_sub(w, w, t2);
-  f2_mul_xi(w, w);
-  f2_add(o.c[0], t0, w);  // t0 + xi (a1 b2 + a2 b1)
-  f2_add(s, a.c[0], a.c[1]);
-  f2_add(u, b.c[0], b.c[1]);
-  f2_mul(w, s, u);
-  f2_sub(w, w, t0);
-  f2_sub(w, w, t1);
-  f2_mul_xi(s, t2);
-  f2_add(o.c[1], w, s);  // a0 b1 + a1 b0 + xi t2
-  f2_add(s, a.c[0], a.c[2]);
-  f2_add(u, b.c[0], b.c[2]);
-  f2_mul(w, s, u);
-  f2_sub(w, w, t0);
-  f2_sub(w, w, t2);
-  f2_add(o.c[2], w, t1);  // a0 b2 + a2 b0 + t1
-  r = o;
-}
-// The inverse of a != 0 as adj / n: adj = a^(p^2) a^(p^4) in Fp6 and the norm
-// n = a adj in Fp2, n != 0.
-HG_DEV void f6_adj_norm(Fp6& adj, Fp2& n, const Fp6& a) {
-  Fp2 A, B, C, t;
-  f2_sqr(A, a.c[0]);
-  f2_mul(t, a.c[1], a.c[2]);
-  f2_mul_xi(t, t);
-  f2_sub(A, A, t);  // a0^2 - xi a1 a2
-  f2_sqr(B, a.c[2]);
-  f2_mul_xi(B, B);
-  f2_mul(t, a.c[0], a.c[1]);
-  f2_sub(B, B, t);  // xi a2^2 - a0 a1
-  f2_sqr(C, a.c[1]);
-  f2_mul(t, a.c[0], a.c[2]);
-  f2_sub(C, C, t);  // a1^2 - a0 a2
-  f2_mul(n, a.c[2], B);
-  f2_mul(t, a.c[1], C);
-  f2_add(n, n, t);
-  f2_mul_xi(n, n);
-  f2_mul(t, a.c[0], A);
-  f2_add(n, n, t);  // a0 A + xi (a2 B + a1 C)
-  adj.c[0] = A;
-  adj.c[1] = B;
-  adj.c[2] = C;
-}
-// one 8-byte aligned element of an entry
-HG_DEV void tor_ld(Fp& v, const uint32_t* p) {
-  const uint2* src = (const uint2*)__builtin_assume_aligned(p, 8);
-#pragma unroll
-  for (int i = 0; i < 5; i++) {
-    const uint2 x = src[i];
-    v.l[2 * i] = x.x;
-    v.l[2 * i + 1] = x.y;
-  }
-}
-HG_DEV void tor_st(uint32_t* p, const Fp& v) {
-  uint2* dst = (uint2*)__builtin_assume_aligned(p, 8);
-#pragma unroll
-  for (int i = 0; i < 5; i++) dst[i] = make_uint2(v.l[2 * i], v.l[2 * i + 1]);
-}
-// the Fp6 halves of an entry: odd = 0 the even powers of w (a), 1 the odd ones (b)
-HG_DEV void tor_load_half(Fp6& r, const Gt* g, int odd) {
-#pragma unroll
-  for (int m = 0; m < 3; m++) {
-    tor_ld(r.c[m].x, g->w + 20 * (2 * m + odd));
-    tor_ld(r.c[m].y, g->w + 20 * (2 * m + odd) + 10);
-  }
-}
-// The entries the conversion walks: the 16-key window table, then the block
-// table. A window entry whose subset holds none of the registry's keys (the
-// empty subset; in a ragged last window also its copies) is 1 and no request
-// names it: it is skipped and keeps its bytes.
-struct TorTables {
-  Gt* win;
-  Gt* blk;
-  size_t nwin, nblk;  // entries
-  int nreg;
-};
-HG_DEV Gt* tor_entry(const TorTables& t, size_t idx) {
-  if (idx < t.nwin) {
-    const int w = (int)(idx >> 16), have = min(16, t.nreg - 16 * w);
-    return ((uint32_t)idx & ((1u << have) - 1u) & 0xffffu) ? t.win + idx : nullptr;
-  }
-  return idx < t.nwin + t.nblk ? t.blk + (idx - t.nwin) : nullptr;
-}
-// flag |= 1 when an entry has b = 0 (nothing is written)
-__global__ __launch_bounds__(256) void k_tor_scan(TorTables t, int* flag) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const Gt* g = tor_entry(t, idx);
-  if (!g) return;
-  uint32_t any = 0;
-#pragma unroll
-  for (int m = 0; m < 3; m++) {
-    const uint4* p = reinterpret_cast<const uint4*>(g->w + 20 * (2 * m + 1));  // 80-byte offsets of a 16-aligned entry
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-      const uint4 v = p[i];
-      any |= v.x | v.y | v.z | v.w;
-    }
-  }
-  if (any == 0) atomicOr(flag, 1);
-}
-// In place, one thread per run of kTorRun consecutive entries. With
-// b^-1 = adj(b) / n(b), n in Fp2, alpha = (1 + a) adj(b) / n(b): the forward
-// pass leaves M = (1 + a) adj(b) in elements 0..5 of the entry, n in elements
-// 6, 7 and the product of the run's earlier norms in elements 8, 9; one Fp2
-// inversion per run (Montgomery's trick over the norms); the backward pass
-// writes alpha = M / n to elements 0..5 and zero to the rest.
-static constexpr int kTorRun = 16;
-__global__ __launch_bounds__(64) void k_tor_convert(TorTables t) {
-  const size_t first = ((size_t)blockIdx.x * 64 + threadIdx.x) * kTorRun;
-  Fp2 acc;
-  f2_one(acc);
-#pragma unroll 1
-  for (int i = 0; i < kTorRun; i++) {
-    Gt* g = tor_entry(t, first + i);
-    if (!g) continue;
-    Fp6 a, b, adj;
-    Fp2 n;
-    tor_load_half(b, g, 1);
-    f6_adj_norm(adj, n, b);
-    tor_load_half(a, g, 0);
-    Fp one;
-    fp_one(one);
-    fp_add(a.c[0].y, a.c[0].y, one);
-    f6_mul(a, a, adj);
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-      tor_st(g->w + 20 * m, a.c[m].x);
-      tor_st(g->w + 20 * m + 10, a.c[m].y);
-    }
-    tor_st(g->w + 60, n.x);
-    tor_st(g->w + 70, n.y);
-    tor_st(g->w + 80, acc.x);
-    tor_st(g->w + 90, acc.y);
-    f2_mul(acc, acc, n);
-  }
-  Fp2 inv;
-  f2_inv(inv, acc);
-  Fp zero;
-  fp_zero(zero);
-#pragma unroll 1
-  for (int i = kTorRun - 1; i >= 0; i--) {
-    Gt* g = tor_entry(t, first + i);
-    if (!g) continue;
-    Fp2 n, pre, ni;
-    tor_ld(n.x, g->w + 60);
-    tor_ld(n.y, g->w + 70);
-    tor_ld(pre.x, g->w + 80);
-    tor_ld(pre.y, g->w + 90);
-    f2_mul(ni, inv, pre);  // 1 / n_i
-    f2_mul(inv, inv, n);   // the inverse of the product before i
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-      Fp2 c;
-      tor_ld(c.x, g->w + 20 * m);
-      tor_ld(c.y, g->w + 20 * m + 10);
-      f2_mul(c, c, ni);
-      tor_st(g->w + 20 * m, c.x);
-      tor_st(g->w + 20 * m + 10, c.y);
-    }
-#pragma unroll
-    for (int e = 6; e < 12; e++) tor_st(g->w + 10 * e, zero);
-  }
-}
-
+// ------------------------------------------------------------------ the fold over tables in torus form (bn256_gttab.hip)
 using ITorF = XInst<XP_TORMULF, S_A, S_A, S_B>;  // A = A * (alpha + w), alpha in elements 0..5 of B
 HG_DEV void tor_mul(const Team& T, XStream& S) {
   team_sync();
   ITorF::run(T, S, xh<ITorF>());
 }
 // element e of a torus entry (e < 6)
-HG_DEV void tor_read(Fp& v, const Gt* g, int e) { tor_ld(v, g->w + 10 * e); }
+HG_DEV void tor_read(Fp& v, const Gt* g, int e) { ld_fp_g8(v, g->w + 10 * e); }
 // lanes 0..5: element tl of slot B = +-alpha
 HG_DEV void tor_put(const Team& T, const Fp& v0, bool conj) {
   Fp v = v0, n;
@@ -820,26 +431,9 @@ __global__ __launch_bounds__(64, HG_CHUNK_WAVES) void k_tor_chunks(const Gt* win
   for (int base = blockIdx.x * kTeams12; base < total; base += gridDim.x * kTeams12) {  // wave-uniform
     const int k = base + team;
     const bool valid = k < total && T.active;
-    int first = 0, cnt = 0, r = 0, c = 0;
-    bool single = false;
-    if (valid) {
-      const int2 e = k < nlong ? ord[k] : ord[cap - 1 - (k - nlong)];
-      c = e.x;
-      r = e.y;
-      const GtReq g = plan[r];
-      first = g.term_off + (c - g.chunk_off) * chunk;
-      cnt = min(chunk, g.term_off + g.m - first);
-      single = g.chunks == 1;
-    }
-    int maxc = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) maxc = max(maxc, __shfl_xor(maxc, d));
-    const uint32_t my_t = T.tl < cnt ? terms[first + T.tl] : 0u;
-    const int tbase = 12 * team;
-    auto term = [&](int i) -> uint32_t {  // wave-uniform i: every lane runs the shuffle
-      const uint32_t v = (uint32_t)__shfl((int)my_t, tbase + (i < 12 ? i : 0), 64);
-      return i < 12 ? v : (i < cnt ? terms[first + i] : 0u);
-    };
+    const FoldChunk ch = fold_chunk(valid, k, nlong, ord, cap, plan, chunk);
+    const int cnt = ch.cnt, maxc = wave_max(cnt);
+    const TermWindow term(T, team, terms, ch);
     // X = +-alpha + w: element 2k + c of an even k is alpha's element k + c,
     // element 3 (the real part of w's coefficient) is one, the rest zero
     Fp cur, n1, n2, one;
@@ -874,7 +468,7 @@ __global__ __launch_bounds__(64, HG_CHUNK_WAVES) void k_tor_chunks(const Gt* win
       if (pad) lds_fp12_copy(T, slot(T, S_A), slot(T, S_F));
     }
     team_sync();
-    if (valid) gt_store(T, S_A, single ? y + r : partial + c);
+    if (valid) gt_store(T, S_A, ch.single ? y + ch.r : partial + ch.c);
     team_sync();
   }
 }
@@ -920,21 +514,6 @@ __global__ __launch_bounds__(64) void k_tor_compare_bits(const Gt* fe, const Gt*
 }
 
 // ------------------------------------------------------------------ launchers
-void launch_gt_keys(const PointG2* reg, int n, const LineCoef* tab, const PointG1* h, Gt* out, hipStream_t s) {
-  if (n > 0) k_gt_keys<4><<<nblk(n, 4), 64, 0, s>>>(reg, n, tab, h, out);
-}
-void launch_gt_windows8(const Gt* key, int nreg, Gt* w8, int nwin8, hipStream_t s) {
-  if (nwin8 <= 0) return;
-  k_gt_nib<<<nblk(2 * nwin8, 4), 64, 0, s>>>(key, nreg, nwin8, w8);
-  k_gt_cross<<<nblk(15 * nwin8, 4), 64, 0, s>>>(nwin8, w8);
-}
-void launch_gt_windows16(const Gt* w8, int nwin8, Gt* w16, int nwin16, hipStream_t s) {
-  if (nwin16 <= 0) return;
-  k_gt_win16<<<nblk(256 * nwin16, kTeams12), 64, 0, s>>>(w8, nwin8, nwin16, w16);
-}
-void launch_gt_blocks(const Gt* src, int stride, int nsrc, Gt* dst, int ndst, hipStream_t s) {
-  if (ndst > 0) k_gt_blocks<<<nblk(ndst, 4), 64, 0, s>>>(src, stride, nsrc, dst, ndst);
-}
 void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_t* codes, int nreg, int levels,
                     const Gt* win, const Gt* blk, const GtBlockIndex& bi, GtWork w, Gt* y, bool zero_hdr, hipStream_t s) {
   if (n <= 0) return;
@@ -952,62 +531,8 @@ void launch_gt_fold(const AggRequest* reqs, int n, const uint64_t* words, int32_
     k_gt_chunks<<<w.chunk_grid, 64, 0, s>>>(win, blk, w.terms, w.ord, w.cap, w.plan, w.hdr, w.chunk, w.partial, y);
   k_gt_combine<<<n, 64, 0, s>>>(n, w.hdr, w.multi, w.plan, w.partial, y);
 }
-void launch_tor_scan(Gt* win, size_t nwin, Gt* blk, size_t nblk_, int nreg, int* flag, hipStream_t s) {
-  const size_t total = nwin + nblk_;
-  (void)hipMemsetAsync(flag, 0, sizeof(int), s);
-  if (total) k_tor_scan<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(TorTables{win, blk, nwin, nblk_, nreg}, flag);
-}
-void launch_tor_convert(Gt* win, size_t nwin, Gt* blk, size_t nblk_, int nreg, hipStream_t s) {
-  const size_t total = nwin + nblk_, per = 64 * kTorRun;
-  if (total) k_tor_convert<<<(unsigned)((total + per - 1) / per), 64, 0, s>>>(TorTables{win, blk, nwin, nblk_, nreg});
-}
 void launch_tor_compare(const Gt* fe, const Gt* x, int n, int32_t* codes, uint8_t* bits, hipStream_t s) {
   if (n > 0) k_tor_compare_bits<<<(n + 7) / 8, 64, 0, s>>>(fe, x, n, codes, bits);
-}
-void launch_verify_sig(const PointG1* sigs, int n, const LineCoef* tab, const Gt* y, int32_t* codes, hipStream_t s) {
-  if (n > 0) k_verify_sig<4, false><<<nblk(n, 4), 64, 0, s>>>(sigs, nullptr, 0, n, tab, y, nullptr, codes);
-}
-// HG_SIG12, HG_SIG12_SPLIT, HG_SIG_W2, HG_SIG_W2_LANE_MAX, HG_VERIFY_SPLIT
-// (bn256_sigform.h SigEnv): the one place that reads them
-const SigEnv& sig_env() {
-  static const SigEnv env = [] {
-    auto on = [](const char* name, bool def) {
-      const char* e = getenv(name);
-      return e ? atoi(e) != 0 : def;
-    };
-    SigEnv v;
-    if (getenv("HG_SIG12")) v.sig12 = on("HG_SIG12", false) ? 1 : 0;
-    v.sig12_split = on("HG_SIG12_SPLIT", true);
-    v.w2 = on("HG_SIG_W2", true);
-    if (const char* e = getenv("HG_SIG_W2_LANE_MAX")) v.w2_lane_max = atoi(e);
-    if (const char* e = getenv("HG_VERIFY_SPLIT")) v.verify_split = atoi(e) == 1;
-    return v;
-  }();
-  return env;
-}
-// the 12-lane and two-wave bodies, in their own units (bn256_sig12.hip;
-// bn256_sigw2.hip, the only one built with HG_TEAM_SPLIT)
-bool launch_sig12(bool pad, bool split, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws,
-                  Gt* fe, hipStream_t s);
-void launch_sig_w2(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s);
-bool launch_sig_form(SigForm f, const uint8_t* sigs, int flavor, int n, const LineCoef* tab, uint8_t* ws, Gt* fe,
-                     hipStream_t s) {
-  switch (f) {
-    case SigForm::W16Pad:
-      if (n > 0) k_verify_sig<4, true><<<nblk(n, 4), 64, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
-      return true;
-    case SigForm::W16:
-      if (n > 0)
-        k_verify_sig<4, true, false><<<nblk(n, 4), 64, 0, s>>>(nullptr, sigs, flavor, n, tab, nullptr, fe, nullptr);
-      return true;
-    case SigForm::T12Pad:
-    case SigForm::T12:
-      return launch_sig12(f == SigForm::T12Pad, sig_form_split(sig_env(), f), sigs, flavor, n, tab, ws, fe, s);
-    case SigForm::W2:
-      launch_sig_w2(sigs, flavor, n, tab, fe, s);
-      return true;
-  }
-  return false;
 }
 void launch_gt_compare(const Gt* fe, const Gt* y, int n, int32_t* codes, hipStream_t s) {
   if (n > 0) k_gt_compare<<<n, 64, 0, s>>>(fe, y, n, codes);

@@ -8,7 +8,7 @@
 // lanes 12..15 evaluate the next G2Base line at -sig beside f^2 — and idle
 // through the final exponentiation, which is ~60 % of the kernel. Here the
 // 85 line evaluations of every signature (b' = bx * x_sig, c' = cy * -y_sig:
-// four Fp products per line, bn256_gt.hip team_miller_sig) run first, as
+// four Fp products per line, bn256_sigteam.h team_miller_sig) run first, as
 // their own wide kernel, into HBM; the pairing kernel then needs only lanes
 // 0..11 of a team, and a wave carries five checks instead of four: 20 % fewer
 // wave-instructions per batch for the same per-wave program (the team
@@ -35,8 +35,8 @@
 
 #include "bn256_decode.h"
 #include "bn256_regs.h"
-#include "bn256_gt.h"
 #include "bn256_sigfe.h"
+#include "bn256_sigpair.h"
 
 namespace hg {
 
@@ -49,7 +49,7 @@ static constexpr int kLineBlock = HG_SIG_LINE_BLOCK;
 
 // the signature's evaluation scalars: sc[2c] = x_sig, sc[2c + 1] = -y_sig
 // (both 0 at infinity: e(inf, G2Base) = 1, every line evaluates to w^3, which
-// the final exponentiation maps to 1 — bn256_gt.hip team_miller_sig). A
+// the final exponentiation maps to 1 — bn256_sigteam.h team_miller_sig). A
 // signature that fails to decode gives meaningless lines: its FE value is
 // never compared (its code is the decode error, k_agg_prologue).
 __global__ __launch_bounds__(kLineBlock) void k_sig_scalars(const uint8_t* sig_bytes, int flavor, int n, Fp* sc) {
@@ -78,9 +78,7 @@ __global__ __launch_bounds__(kLineBlock) void k_sig_lines(const Fp* sc, int n, c
   const Fp b = sc[2 * c + (j >> 1)];
   Fp o;
   fp_mul(o, a, b);
-  uint2* dst = (uint2*)__builtin_assume_aligned(ev + (size_t)s * 4 * n + t, 8);
-#pragma unroll
-  for (int i = 0; i < 5; i++) dst[i] = make_uint2(o.l[2 * i], o.l[2 * i + 1]);
+  st_fp_g8(ev[(size_t)s * 4 * n + t].l, o);
 }
 
 // The evaluated line reaches the team's registers FB, FC through one VGPR
@@ -90,15 +88,7 @@ struct EvPipe {
   Fp c;
 };
 HG_DEV void ev_fetch(const Team& T, EvPipe& P, const Fp* ev, int n, int ci, int s) {
-  if (T.tl < 4) {
-    const uint2* src = (const uint2*)__builtin_assume_aligned(ev + ((size_t)s * n + ci) * 4 + T.tl, 8);
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-      const uint2 x = src[i];
-      P.c.l[2 * i] = x.x;
-      P.c.l[2 * i + 1] = x.y;
-    }
-  }
+  if (T.tl < 4) ld_fp_g8(P.c, ev[((size_t)s * n + ci) * 4 + T.tl].l);
 }
 // the held line into FB, FC, then line `next` into flight
 HG_DEV void ev_publish(const Team& T, uint32_t* F, EvPipe& P, const Fp* ev, int n, int ci, int next) {
@@ -110,7 +100,7 @@ HG_DEV void ev_publish(const Team& T, uint32_t* F, EvPipe& P, const Fp* ev, int 
 using ISqr12T = XInst<XP_SQR12_12_T, S_F, S_F>;
 using ILineT = XInst<XP_LINE_FIX_12_T, S_F, S_F>;
 
-// Miller(G2Base at -sig) over the NAF of 6u + 2 (bn256_gt.hip
+// Miller(G2Base at -sig) over the NAF of 6u + 2 (bn256_sigteam.h
 // team_miller_sig's loop; the lines arrive evaluated): f^2, then f * line
 // per digit (two lines on a nonzero digit), then the two Frobenius lines
 HG_DEV void team_miller_sig12(const Team& T, uint32_t* F, const Fp* ev, int n, int ci, XStream& S, XHint after) {

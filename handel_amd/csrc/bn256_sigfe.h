@@ -1,5 +1,5 @@
 // bn256_sigfe.h — the sig-only pairing kernels' final exponentiation on their
-// compact team regions: k_verify_sig (16-lane teams, layout S, bn256_gt.hip)
+// compact team regions: k_verify_sig (16-lane teams, layout S, bn256_sig16.hip)
 // and k_verify_sig12 (12-lane teams, layout T, bn256_sig12.hip) run the same
 // Fuentes-Castaneda chain, each on its own bound program tables
 // (tools/gen_g2_schedule.py SIG_INSTANCES, SIG_T_INSTANCES).
@@ -32,23 +32,13 @@ struct SigProgs12 {
 HG_DEV void t12_park(const Team& T, int s, uint32_t* park) {
   Fp v;
   ld_fp_a8(v, slot(T, s) + T.e * 10);
-  if (T.active) {
-    uint2* dst = (uint2*)__builtin_assume_aligned(park + 10 * T.e, 8);
-#pragma unroll
-    for (int i = 0; i < 5; i++) dst[i] = make_uint2(v.l[2 * i], v.l[2 * i + 1]);
-  }
+  if (T.active) st_fp_g8(park + 10 * T.e, v);
   __threadfence_block();
 }
 HG_DEV void t12_unpark(const Team& T, int s, const uint32_t* park) {
-  const uint2* src = (const uint2*)__builtin_assume_aligned(park + 10 * T.e, 8);
-  uint32_t v[10];
-#pragma unroll
-  for (int i = 0; i < 5; i++) {
-    const uint2 x = src[i];
-    v[2 * i] = x.x;
-    v[2 * i + 1] = x.y;
-  }
-  if (T.active) st_fp_a8(slot(T, s) + T.e * 10, v);
+  Fp v;
+  ld_fp_g8(v, park + 10 * T.e);
+  if (T.active) st_fp_a8(slot(T, s) + T.e * 10, v.l);
   team_sync(T);
 }
 

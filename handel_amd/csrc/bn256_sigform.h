@@ -1,7 +1,7 @@
 // bn256_sigform.h — which signature-pairing kernel a batch runs: the one
-// chooser of the GT path (FE(Miller(G2Base at -sig)) per check, bn256_gt.hip)
-// and config 2's split bound. Plain C++, nothing from HIP: the rules run on
-// the host (tests/native/sigform_host.cpp). launch_sig_form (bn256_gt.h) runs
+// chooser of the GT path (FE(Miller(G2Base at -sig)) per check) and config
+// 2's split bound. Plain C++, nothing from HIP: the rules run on the host
+// (tests/native/sigform_host.cpp). launch_sig_form (bn256_sigpair.h) runs
 // what sig_form() chose. The forms give the same FE values, bit for bit; they
 // differ in how a check lies over the lanes, so in what a batch costs alone
 // and beside others:
@@ -33,7 +33,7 @@ constexpr int kSigW2MaxN = 2048;
 // the values are hg_sig_pairing_device's `kernel` numbers (include/handel_gpu.h)
 enum class SigForm { W16Pad = 0, W16 = 1, T12Pad = 2, T12 = 3, W2 = 4 };
 
-// the A/B knobs, parsed (sig_env(), bn256_gt.hip, reads them once)
+// the A/B knobs, parsed (sig_env(), bn256_sig16.hip, reads them once)
 struct SigEnv {
   int sig12 = -1;            // HG_SIG12: 1 / 0 forces / forbids the 12-lane forms, -1 (unset) by padding
   bool sig12_split = true;   // HG_SIG12_SPLIT=0: T12 as one kernel
@@ -65,7 +65,7 @@ inline bool sig_form_split(const SigEnv& e, SigForm f) { return f == SigForm::T1
 
 inline bool sig_form_12(SigForm f) { return f == SigForm::T12Pad || f == SigForm::T12; }
 
-// the workspace launch_sig_form (bn256_gt.h) needs for n checks: none but the
+// the workspace launch_sig_form (bn256_sigpair.h) needs for n checks: none but the
 // 12-lane forms' evaluated lines and records (bn256_sig12.hip)
 size_t sig12_lines_bytes(int n);
 inline size_t sig_form_ws_bytes(SigForm f, int n) { return sig_form_12(f) ? sig12_lines_bytes(n) : 0; }

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bn256_decode.h"
-#include "bn256_gt.h"
+#include "bn256_sigpair.h"
 #include "bn256_sigteam.h"
 
 namespace hg {

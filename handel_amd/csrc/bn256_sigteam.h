@@ -1,7 +1,7 @@
 // bn256_sigteam.h — the pieces of the GT path's signature-side pairing that
 // both of its 16-lane kernels use: GT values between HBM and team slots, the
 // Miller loop at -sig (G2Base lines from the table), the layout-S team region.
-// k_verify_sig (bn256_gt.hip) runs them on one wave per team, the latency form
+// k_verify_sig (bn256_sig16.hip) runs them on one wave per team, the latency form
 // k_verify_sig_split (bn256_sigsplit.h) on teams spread over 2 or 4 waves.
 #pragma once
 
@@ -15,15 +15,7 @@ namespace hg {
 // A GT value in HBM is the team slot layout: element e (10 limbs) at w[10 e].
 // Lane e < 12 moves element e; `conj` negates the odd powers of w on the way
 // in (the inverse of a unitary value). No sync: callers sync before reading.
-HG_DEV void gt_read(Fp& v, const Gt* g, const Team& T) {
-  const uint2* src = (const uint2*)__builtin_assume_aligned(g->w + 10 * T.e, 8);
-#pragma unroll
-  for (int i = 0; i < 5; i++) {
-    const uint2 x = src[i];
-    v.l[2 * i] = x.x;
-    v.l[2 * i + 1] = x.y;
-  }
-}
+HG_DEV void gt_read(Fp& v, const Gt* g, const Team& T) { ld_fp_g8(v, g->w + 10 * T.e); }
 HG_DEV void gt_put(const Team& T, int s, const Fp& v0, bool conj) {
   Fp v = v0;
   if (conj) {
@@ -55,10 +47,7 @@ HG_DEV void gt_load_or_one(const Team& T, int s, const Gt* g, bool present) {
 HG_DEV void gt_store(const Team& T, int s, Gt* g) {
   Fp v;
   ld_fp_a8(v, slot(T, s) + T.e * 10);
-  if (!T.active) return;
-  uint2* dst = (uint2*)__builtin_assume_aligned(g->w + 10 * T.e, 8);
-#pragma unroll
-  for (int i = 0; i < 5; i++) dst[i] = make_uint2(v.l[2 * i], v.l[2 * i + 1]);
+  if (T.active) st_fp_g8(g->w + 10 * T.e, v);
 }
 // element-wise copy between team-region Fp12 values (LDS pointers)
 HG_DEV void lds_fp12_copy(const Team& T, uint32_t* dst, const uint32_t* src) {

@@ -7,7 +7,7 @@
 
 namespace hg {
 
-// launch_sig_form's W2 body (bn256_gt.hip)
+// launch_sig_form's W2 body (bn256_sig16.hip)
 void launch_sig_w2(const uint8_t* sigs, int flavor, int n, const LineCoef* tab, Gt* fe, hipStream_t s) {
   if (n > 0) k_verify_sig_split<2><<<(n + 3) / 4, 64 * 2, 0, s>>>(sigs, flavor, n, tab, fe);
 }

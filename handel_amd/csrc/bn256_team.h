@@ -69,6 +69,20 @@ HG_DEV void st_fp_a8(uint32_t* p, const uint32_t* l) {
 #pragma unroll
   for (int i = 0; i < 5; i++) q[i] = (uint64_t)l[2 * i] | ((uint64_t)l[2 * i + 1] << 32);
 }
+HG_DEV void ld_fp_g8(Fp& r, const uint32_t* p) {  // the same element in HBM, as five 8-byte words
+  const uint2* src = (const uint2*)__builtin_assume_aligned(p, 8);
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const uint2 x = src[i];
+    r.l[2 * i] = x.x;
+    r.l[2 * i + 1] = x.y;
+  }
+}
+HG_DEV void st_fp_g8(uint32_t* p, const Fp& a) {
+  uint2* dst = (uint2*)__builtin_assume_aligned(p, 8);
+#pragma unroll
+  for (int i = 0; i < 5; i++) dst[i] = make_uint2(a.l[2 * i], a.l[2 * i + 1]);
+}
 HG_DEV void ld_f2(Fp2& r, const uint32_t* f12, int k) {
   ld_fp(r.x, f12 + (2 * k) * 10);
   ld_fp(r.y, f12 + (2 * k + 1) * 10);

@@ -4,8 +4,8 @@
 #define HG_DIAG_TU 1
 #include <hip/hip_runtime.h>
 
-#include "bn256_gt.h"
 #include "bn256_pairing.h"
+#include "bn256_sigpair.h"
 
 namespace hg {
 static inline int nblk(int n, int b) { return (n + b - 1) / b; }

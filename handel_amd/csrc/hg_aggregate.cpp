@@ -372,35 +372,37 @@ static void gt_fold(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, int3
                  gw.win_bits == 16 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, zero_hdr,
                  s);
 }
-// the pairing in its stored form and the comparison with the fold's values:
-// how every flow ends on a table set in torus form, where gt_y holds X
-// (launch_tor_compare) and k_verify_sig's own comparison cannot be used
-static int pair_and_compare(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipStream_t s) {
-  const int n = (int)b.n;
+// the pairing in its stored form (the batch's): fe[r] = FE(Miller(G2Base at -sig_r))
+static int pair_stored(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipStream_t s) {
   PhaseTimer t(c, HG_PHASE_VERIFY, s);
-  const bool ran = launch_sig_form(form, b.sigs, c->flavor, n, c->d_lines.p, ws.sig_lines.p, ws.gt_fe.p, s);
+  const bool ran = launch_sig_form(form, b.sigs, c->flavor, (int)b.n, c->d_lines.p, ws.sig_lines.p, ws.gt_fe.p, s);
   t.stop();
   if (!ran) {
     c->err = "aggregate batch too large for its pairing form";
     return HG_ERR_ARG;
   }
-  launch_tor_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
   return HG_OK;
+}
+// the stored FE values against gt_y: the fold's X on a torus set (the verdict bitset with it), else Y
+static void compare_stored(const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
+  if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.gt_y.p, (int)b.n, b.codes, b.bits, s);
+  else if (b.bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, (int)b.n, b.codes, b.bits, s);
+  else launch_gt_compare(ws.gt_fe.p, ws.gt_y.p, (int)b.n, b.codes, s);
+}
+// both: how a flow that folds first ends on a torus set (k_verify_sig's own comparison cannot be used)
+static int pair_and_compare(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, const GtWork& gw, hipStream_t s) {
+  const int rc = pair_stored(c, b, ws, form, s);
+  if (rc == HG_OK) compare_stored(b, ws, gw, s);
+  return rc;
 }
 
 // GT path, verdicts only, the fold beside the pairing:
 // s:    pairing (decodes its signatures) ............ -> wait -> compare
 // side: wait -> prologue (codes, counters), plan, chunks, combine -> join
 static int flow_gt_beside(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, const GtWork& gw, hipStream_t s) {
-  const int n = (int)b.n;
   HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
-  PhaseTimer t(c, HG_PHASE_VERIFY, s);
-  const bool ran = launch_sig_form(form, b.sigs, c->flavor, n, c->d_lines.p, ws.sig_lines.p, ws.gt_fe.p, s);
-  t.stop();
-  if (!ran) {
-    c->err = "aggregate batch too large for its pairing form";
-    return HG_ERR_ARG;
-  }
+  int rc = pair_stored(c, b, ws, form, s);
+  if (rc) return rc;
   HG_CHECK(c, hipStreamWaitEvent(ws.side, ws.ev_fork, 0));
   gt_prologue(c, b, ws, gw, ws.side);
   PhaseTimer fold(c, HG_PHASE_AGGREGATE, ws.side);
@@ -408,9 +410,7 @@ static int flow_gt_beside(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, co
   fold.stop();
   HG_CHECK(c, hipEventRecord(ws.ev_join, ws.side));
   HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
-  if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
-  else if (b.bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, n, b.codes, b.bits, s);
-  else launch_gt_compare(ws.gt_fe.p, ws.gt_y.p, n, b.codes, s);
+  compare_stored(b, ws, gw, s);
   return HG_OK;
 }
 
@@ -422,7 +422,7 @@ static int flow_gt_sequence(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, 
   PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
   gt_fold(c, b, ws, gw, b.codes, false, s);
   fold.stop();
-  if (gw.torus) return pair_and_compare(c, b, ws, form, s);
+  if (gw.torus) return pair_and_compare(c, b, ws, form, gw, s);
   PhaseTimer t(c, HG_PHASE_VERIFY, s);
   launch_verify_sig(ws.pts1.p, n, c->d_lines.p, ws.gt_y.p, b.codes, s);
   t.stop();
@@ -455,7 +455,7 @@ static int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, b
     launch_decode_g1(b.sigs, n, c->flavor, ws.pts1.p, ws.codes_b.p, s);
     k_agg_codes<<<nb(b.n), 256, 0, s>>>(ws.codes_b.p, d_lvl, c->cur.hash_eof ? 1 : 0, n, b.codes);
     if (use_gt && gw.torus) {
-      return pair_and_compare(c, b, ws, form, s);  // the verdict bitset with it
+      return pair_and_compare(c, b, ws, form, gw, s);  // the verdict bitset with it
     } else if (use_gt) {
       PhaseTimer t(c, HG_PHASE_VERIFY, s);
       launch_verify_sig(ws.pts1.p, n, c->d_lines.p, ws.gt_y.p, b.codes, s);

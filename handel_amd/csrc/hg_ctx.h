@@ -17,6 +17,7 @@
 
 #include "bn256_gt.h"
 #include "bn256_kernels.h"
+#include "bn256_sigpair.h"
 #include "hg_codes.h"
 #include "hg_dev.h"
 #include "hg_packets.h"
@@ -66,7 +67,7 @@ struct TableSet {
   std::vector<uint8_t> msg;  // the message d_h was hashed from (hg_*_msg cache)
   bool has_msg = false, hash_eof = false;
   DevBuf<PointG1> d_h;  // one point, allocated on the set's first message
-  // GT path of aggregate verification (bn256_gt.hip): e(H, pk_i), window
+  // GT path of aggregate verification (bn256_gttab.hip): e(H, pk_i), window
   // subset products (gt_w8: 8-key windows, gt_win: 16-key windows) and block
   // products, valid for this message and the registry (rebuilt by the first
   // aggregate submission after either changes)
@@ -76,7 +77,7 @@ struct TableSet {
   // raised by hg_prepare_aggregate or by request volume (gt_requests).
   int gt_level = 0;
   // the form of gt_win and gt_blk, meaningful at gt_level 2 (set by every
-  // level-2 build): torus form (bn256_gt.hip), which only k_tor_chunks reads,
+  // level-2 build): torus form (bn256_gttab.hip), which only k_tor_chunks reads,
   // so a torus set folds over its 16-key windows whatever level a submission
   // asks for; false: Fp12 (the conversion is off, or an entry has no torus form)
   bool torus = false;

@@ -228,7 +228,7 @@ struct hg_service {
 #ifdef HG_SERVICE_TESTING
   uint32_t test_finish_us = 0;  // HG_SERVICE_TEST_FINISH_US
 #endif
-  static constexpr int kW2MaxChecks = 2048;  // the latency form's largest batch (bn256_gt.h kSigW2MaxN)
+  static constexpr int kW2MaxChecks = 2048;  // the latency form's largest batch (bn256_sigform.h kSigW2MaxN)
 
   bool intake();
   void complete(int lane, const int32_t* codes, int32_t fail);

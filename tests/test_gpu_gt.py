@@ -1,4 +1,6 @@
-"""GPU suite: the GT path of aggregate verification (handel_amd/csrc/bn256_gt.hip).
+"""GPU suite: the GT path of aggregate verification (handel_amd/csrc:
+bn256_gt.hip the fold, bn256_gttab.hip its tables, bn256_sig16.hip the
+signature pairing).
 
 hg_verify_aggregate checks e(H, sum of set keys) == e(sig, G2Base) as
 FE(Miller(G2Base at -sig)) == conj(prod of per-key GT values), with the
@@ -168,8 +170,10 @@ def test_gt_and_g2_paths_agree():
     16-key windows (HG_GT_LEVEL=2), over 8-key windows (1), the G2 point fold
     + two-pairing check (0, and HG_AGG_PATH=g2) — each in a child process."""
     outs = {}
-    # gt16c16 / gt16c5: chunks of 16 and 5 terms per fold team (HG_GT_CHUNK):
-    # a 12-lane team (k_gt_chunks) reads terms past 12 from the term list
+    # chunks of 16 and 5 terms per fold team (HG_GT_CHUNK): a 12-lane team
+    # holds its first 12 terms and reads terms past 12 from the term list.
+    # Level 2 is in torus form, so gt16c16 / gt16c5 run k_tor_chunks; gt8c16
+    # (level 1) and gt16c16fp12 (level 2 kept in Fp12 form) run k_gt_chunks
     runs = (("gt16", {"HG_GT_LEVEL": "2"}), ("gt8", {"HG_GT_LEVEL": "1"}),
             ("g2", {"HG_GT_LEVEL": "0"}), ("g2env", {"HG_AGG_PATH": "g2"}),
             ("gt16c16", {"HG_GT_LEVEL": "2", "HG_GT_CHUNK": "16"}),
@@ -180,10 +184,12 @@ def test_gt_and_g2_paths_agree():
             # HG_SIG_W2=0)
             ("gt16sig12", {"HG_GT_LEVEL": "2", "HG_SIG12": "1"}),
             ("gt16sig16", {"HG_GT_LEVEL": "2", "HG_SIG12": "0"}),
-            ("gt16w1", {"HG_GT_LEVEL": "2", "HG_SIG12": "0", "HG_SIG_W2": "0"}))
+            ("gt16w1", {"HG_GT_LEVEL": "2", "HG_SIG12": "0", "HG_SIG_W2": "0"}),
+            ("gt8c16", {"HG_GT_LEVEL": "1", "HG_GT_CHUNK": "16"}),
+            ("gt16c16fp12", {"HG_GT_LEVEL": "2", "HG_GT_TORUS": "0", "HG_GT_CHUNK": "16"}))
     for name, env in runs:
         outs[name] = _child(env)
-    assert [outs[k]["level"] for k, _ in runs] == [2, 1, 0, 0, 2, 2, 2, 2, 2]
+    assert [outs[k]["level"] for k, _ in runs] == [2, 1, 0, 0, 2, 2, 2, 2, 2, 1, 2]
     assert all(outs[k]["codes"] == outs["gt16"]["codes"] for k, _ in runs)
     import bench
     from handel_amd.engine import Engine

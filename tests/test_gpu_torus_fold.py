@@ -1,5 +1,6 @@
-"""GPU suite: the GT fold over tables in torus form (handel_amd/csrc/bn256_gt.hip
-k_tor_scan, k_tor_convert, k_tor_chunks, k_tor_compare_bits; hg_aggregate.cpp).
+"""GPU suite: the GT fold over tables in torus form (handel_amd/csrc:
+bn256_gttab.hip k_tor_scan, k_tor_convert; bn256_gt.hip k_tor_chunks,
+k_tor_compare_bits; hg_aggregate.cpp).
 
 At table level 2 the 16-key window table and the block table keep each entry
 g = a + b w as alpha = (1 + a)/b, and the fold multiplies a running X (value

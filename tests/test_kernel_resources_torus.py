@@ -1,4 +1,5 @@
-"""The torus fold's kernels (handel_amd/csrc/bn256_gt.hip) keep the budgets
+"""The torus fold's kernels (handel_amd/csrc/bn256_gt.hip; the table
+conversion: bn256_gttab.hip) keep the budgets
 DESIGN.md §3a argues from: k_tor_chunks runs in k_gt_chunks' place, so it has
 its LDS (12 000 B: five 12-lane teams of the 60-element fold region) and at
 most its 212 VGPRs, and a fold workgroup still fits beside eight pairing waves

@@ -542,9 +542,10 @@ PROGRAMS = {
     "PADD_F2": prog_add_proj("P2X", "QY"),
 }
 # The G2Base lines are normalised (a = 1): LINE_FIX = prog_line_n.
-# Sig-only Miller loop (bn256_gt.hip k_verify_sig): the G2Base line at -sig is
-# evaluated on lanes 12..15 beside f^2 (SDBL) or beside f * the previous line
-# (LFEV), rounds whose Fp12 jobs leave those lanes idle anyway; FEVAL alone.
+# Sig-only Miller loop (bn256_sigteam.h team_miller_sig, run by k_verify_sig):
+# the G2Base line at -sig is evaluated on lanes 12..15 beside f^2 (SDBL) or
+# beside f * the previous line (LFEV), rounds whose Fp12 jobs leave those lanes
+# idle anyway; FEVAL alone.
 PROGRAMS["FEVAL"] = [fixed_line_eval()]
 PROGRAMS["SDBL"] = [prog_sqr12()[0] + fixed_line_eval()]
 PROGRAMS["LFEV"] = [prog_line_n("FB", "FC")[0] + fixed_line_eval()]
@@ -971,7 +972,7 @@ KARATSUBA_MIN = 4   # jobs of this many products use Karatsuba (when check_xroun
 # instruction count decides (Karatsuba from four products on).
 KARATSUBA_MIN_PROG = {"CYC_SQR_X_12": 3, "TORMULF": 4}
 # FE: the register file from register 2 on; ML: slots C..J during the Miller loop
-# FOLD: the GT fold kernels' compact team region (bn256_gt.hip): slots F, A, B,
+# FOLD: the GT fold kernels' compact team region (bn256_gtfold.h): slots F, A, B,
 # then registers ZERO and ONE, then the pre-pass scratch
 SCRATCH_CAP = {"FE": 48, "ML": 96, "FOLD": 48}
 X_PROGRAMS = {  # name -> (program, scratch context)
@@ -1230,10 +1231,10 @@ INSTANCES = sorted(set(
     + [("CYC_SQR_X", ("B", "A")), ("CYC_SQR", ("I", "C"))]
     + [("MUL12", b) for b in [("B", "A", "B"), ("B", "C", "D"), ("E", "B", "J"), ("D", "A", "E"), ("A", "C", "E"),
                               ("A", "F", "A"), ("A", "G", "A"), ("G", "G", "D"), ("F", "G", "A")]]
-    # bn256_gt.hip: the GT fold
+    # bn256_gtfold.h: the GT fold and its table builders
     + [("MUL12F", ("A", "A", "B"))]))
 
-# k_verify_sig's compact team region (layout "S", bn256_gt.hip): slots F, A, B,
+# k_verify_sig's compact team region (layout "S", bn256_sig16.hip): slots F, A, B,
 # C, D, E, G — the sig-only Miller loop and the Fuentes-Castaneda final
 # exponentiation (team_final_exp_fc_s) need no more — then the register file.
 # The Miller loop's pre-pass scratch lies in slots A.. (only F is live there),
@@ -1563,7 +1564,7 @@ def check_instances(X, seed=3):
                 assert mem[fb + r] == v, f"instance {name} reg {r}"
 
 
-# the programs k_verify_sig runs (bn256_gt.hip: the sig-only Miller loop and
+# the programs k_verify_sig runs (bn256_sig16.hip: the sig-only Miller loop and
 # the final exponentiation); its team region ends after the last element they
 # (and the hand-written helpers: registers up to FC) touch
 SIG_PROGRAMS = ("SDBL", "LFEV", "FEVAL", "LINE_FIX", "MUL12", "CYC_SQR_X", "CYC_SQR",

@@ -5,7 +5,7 @@ per kernel by class (VALU, v_mad_u64_u32, SALU, LDS, VMEM, branch). A build-time
 proxy for instruction-count changes (dynamic counts come from the SQ_INSTS_*
 PMC passes on the GPU box).
 
-  python tools/isa_count.py handel_amd/_build/bn256_gt.o [name-regex]
+  python tools/isa_count.py handel_amd/_build/bn256_sig16.o [name-regex]
 """
 
 import re
