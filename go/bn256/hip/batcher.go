@@ -17,8 +17,9 @@ type job struct {
 
 // batcher merges concurrent PublicKey.VerifySignature calls into launches
 // (SURVEY.md §8(b) option 1: no Handel change). One goroutine takes the
-// first queued job, drains whatever else is queued (up to maxBatch), groups
-// the jobs by message and kind, and submits each group as one C call. There
+// first queued job, drains whatever else is queued (up to maxBatch) and
+// submits it (flush): the single checks as one launch whatever their messages,
+// the aggregate checks as one C call per message. There
 // is no timer: while one launch runs the next batch accumulates, so the batch
 // width follows the number of concurrent callers (k Handel instances per
 // process, simul/node/main.go:63-131) without adding latency to a lone caller.
@@ -71,47 +72,55 @@ func (b *batcher) run() {
 	}
 }
 
-type groupKey struct {
-	msg string
-	agg bool
-}
-
+// flush submits one drained set of jobs. Every single-signature job goes into
+// ONE VerifyBatchMsgs call, each check on its own message (hashedMessage runs
+// per check on the device), so callers on different messages still share a
+// launch. Aggregate jobs need the per-message GT tables of the context and stay
+// grouped by message, one C call per group.
 func (b *batcher) flush(jobs []*job) {
-	groups := map[groupKey][]*job{}
-	var order []groupKey
+	var ones []*job
+	groups := map[string][]*job{}
+	var order []string
 	for _, j := range jobs {
-		k := groupKey{string(j.msg), j.agg != nil}
+		if j.agg == nil {
+			ones = append(ones, j)
+			continue
+		}
+		k := string(j.msg)
 		if _, ok := groups[k]; !ok {
 			order = append(order, k)
 		}
 		groups[k] = append(groups[k], j)
 	}
+	if len(ones) > 0 {
+		msgs := make([][]byte, len(ones))
+		pks := make([]byte, 0, 128*len(ones))
+		sigs := make([]byte, 0, 64*len(ones))
+		for i, j := range ones {
+			msgs[i] = j.msg
+			pks = append(pks, j.one.pk...)
+			sigs = append(sigs, j.one.sig...)
+		}
+		codes, err := b.e.VerifyBatchMsgs(msgs, pks, sigs)
+		b.finish(ones, codes, err)
+	}
 	for _, k := range order {
 		g := groups[k]
-		msg := []byte(k.msg)
-		var codes []int32
-		var err error
-		if k.agg {
-			reqs := make([]Request, len(g))
-			for i, j := range g {
-				reqs[i] = *j.agg
-			}
-			codes, _, err = b.e.VerifyAggregate(msg, reqs, false)
-		} else {
-			pks := make([]byte, 0, 128*len(g))
-			sigs := make([]byte, 0, 64*len(g))
-			for _, j := range g {
-				pks = append(pks, j.one.pk...)
-				sigs = append(sigs, j.one.sig...)
-			}
-			codes, err = b.e.VerifyBatch(msg, pks, sigs)
-		}
+		reqs := make([]Request, len(g))
 		for i, j := range g {
-			if err != nil {
-				j.done <- err // the whole submission failed: no verdict, not "valid"
-			} else {
-				j.done <- b.e.CodeError(codes[i])
-			}
+			reqs[i] = *j.agg
+		}
+		codes, _, err := b.e.VerifyAggregate([]byte(k), reqs, false)
+		b.finish(g, codes, err)
+	}
+}
+
+func (b *batcher) finish(g []*job, codes []int32, err error) {
+	for i, j := range g {
+		if err != nil {
+			j.done <- err // the whole submission failed: no verdict, not "valid"
+		} else {
+			j.done <- b.e.CodeError(codes[i])
 		}
 	}
 }

@@ -260,6 +260,44 @@ func (e *Engine) VerifyBatch(msg, pks, sigs []byte) ([]int32, error) {
 	return codes, nil
 }
 
+// VerifyBatchMsgs runs n = len(msgs) independent PublicKey.VerifySignature(
+// msgs[i], sig_i) checks (bn256/go/bn256.go:82-94), each on its own message, in
+// one launch (hg_verify_batch_msgs): hashedMessage runs per check on the
+// device. The context's current message and its tables stay as they are.
+// Equal messages (compared as strings) are stored once.
+func (e *Engine) VerifyBatchMsgs(msgs [][]byte, pks, sigs []byte) ([]int32, error) {
+	n := len(msgs)
+	if len(sigs) != 64*n || len(pks) != 128*n {
+		return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyBatchMsgs: msgs/pks/sigs sizes"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	off := make([]uint32, n)
+	ln := make([]uint32, n)
+	seen := map[string]uint32{}
+	var pool []byte
+	for i, m := range msgs {
+		at, ok := seen[string(m)]
+		if !ok {
+			if uint64(len(pool))+uint64(len(m)) >= 1<<32 {
+				return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyBatchMsgs: messages above 4 GiB"}
+			}
+			at = uint32(len(pool))
+			seen[string(m)] = at
+			pool = append(pool, m...)
+		}
+		off[i], ln[i] = at, uint32(len(m))
+	}
+	codes := failedCodes(n)
+	rc := C.hg_verify_batch_msgs(e.ctx, bytePtr(pool), C.size_t(len(pool)), (*C.uint32_t)(unsafe.Pointer(&off[0])),
+		(*C.uint32_t)(unsafe.Pointer(&ln[0])), bytePtr(pks), bytePtr(sigs), C.size_t(n), codePtr(codes))
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
+	}
+	return codes, nil
+}
+
 // Request is one aggregate check (processing.go:342-368 verifySignature):
 // the level's registry range starts at Offset and has LevelSize keys; Words
 // holds the bitset (willf layout: bit i = Words[i>>6] bit i&63) of BitLen

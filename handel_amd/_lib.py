@@ -91,6 +91,11 @@ SIGNATURES = {
     "hg_verify_batch": (_I, [_P, _P, _P, _SZ, _P]),
     "hg_verify_batch_msg": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
     "hg_verify_batch_device": (_I, [_P, _P, _P, _SZ, _P, _P]),
+    "hg_verify_batch_msgs": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
+    "hg_verify_batch_msgs_device": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _P]),
+    "hg_hash_messages": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
+    "hg_debug_g1_base_mul": (_I, [_P, _P, _SZ, _P]),
+    "hg_debug_hash_scalar": (_I, [_P, _SZ, _P]),
     "hg_pack_verdicts_device": (_I, [_P, _P, _SZ, _P, _P]),
     "hg_verify_aggregate": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P]),
     "hg_verify_aggregate_device": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),

@@ -98,6 +98,23 @@ class PublicKey(_Base):
         return BN256Error(e.code_string(int(codes[0])))
 
 
+def VerifySignatures(pks, msgs, sigs):
+    """pks[i].VerifySignature(msgs[i], sigs[i]) for every i in ONE batch, each
+    check on its own message (Engine.verify_batch_msgs): a list of None /
+    BN256Error as the single call returns them. The keys' flavor decides the
+    unmarshal rules; the shared context's current message is not touched."""
+    if not (len(pks) == len(msgs) == len(sigs)):
+        raise ValueError("one message and one signature per key")
+    if not pks:
+        return []
+    for pk in pks:
+        if pk.p is None:
+            raise BN256Error("runtime error: invalid memory address or nil pointer dereference")
+    e = pks[0]._eng()
+    codes = e.verify_batch_msgs(list(msgs), b"".join(pk.p for pk in pks), b"".join(s.MarshalBinary() for s in sigs))
+    return [None if c == HG_OK else BN256Error(e.code_string(int(c))) for c in codes]
+
+
 class SigBLS(_Base):
     """bn256/go/bn256.go:168-204: a G1 point."""
 

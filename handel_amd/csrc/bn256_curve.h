@@ -123,6 +123,55 @@ HG_DEV void g1_add(G1J& r, const G1J& a, const G1J& b) {
   r.z = z3;
 }
 
+// mixed addition a + (bx, by) with b affine (madd-2007-bl, as g2_madd): a at
+// infinity, a == b (doubling) and a == -b (infinity) handled as in g1_add.
+// Used by the fixed-base multiplication of the per-check hashes.
+HG_DEV void g1_madd(G1J& r, const G1J& a, const Fp& bx, const Fp& by) {
+  if (g1_is_inf(a)) {
+    r.x = bx;
+    r.y = by;
+    fp_one(r.z);
+    return;
+  }
+  Fp z1z1, u2, s2, h, hh, i, j, rr, v, t, x3, y3, z3;
+  fp_sqr(z1z1, a.z);
+  fp_mul(u2, bx, z1z1);
+  fp_mul(t, a.z, z1z1);
+  fp_mul(s2, by, t);
+  fp_sub(h, u2, a.x);
+  fp_sub(rr, s2, a.y);
+  if (fp_is_zero(h)) {
+    if (fp_is_zero(rr)) {
+      g1_double(r, a);
+    } else {
+      g1_set_inf(r);
+    }
+    return;
+  }
+  fp_sqr(hh, h);
+  fp_dbl(i, hh);
+  fp_dbl(i, i);
+  fp_mul(j, h, i);
+  fp_dbl(rr, rr);
+  fp_mul(v, a.x, i);
+  fp_sqr(x3, rr);
+  fp_sub(x3, x3, j);
+  fp_sub(x3, x3, v);
+  fp_sub(x3, x3, v);
+  fp_sub(t, v, x3);
+  fp_mul(y3, rr, t);
+  fp_mul(t, a.y, j);
+  fp_dbl(t, t);
+  fp_sub(y3, y3, t);
+  fp_add(t, a.z, h);
+  fp_sqr(t, t);
+  fp_sub(t, t, z1z1);
+  fp_sub(z3, t, hh);
+  r.x = x3;
+  r.y = y3;
+  r.z = z3;
+}
+
 // k * a for a 256-bit scalar given as 8 LE 32-bit words (double-and-add, MSB first)
 HG_DEV void g1_mul(G1J& r, const G1J& a, const uint32_t* k) {
   G1J acc;

@@ -52,6 +52,31 @@ void launch_verify(const CheckIn* in, int n, const LineCoef* tab, const PointG1*
 size_t verify_split_ws_bytes(int n);
 bool launch_verify_split(const CheckIn* in, int n, const LineCoef* tab, const PointG1* h, int32_t* codes,
                          uint8_t* ws, hipStream_t s);
+// the split form's pieces for the per-check-H kernels (bn256_msgs.hip): the
+// bytes of the Miller values at the head of the workspace, and k_fe_verdicts
+size_t verify_split_fe_bytes(int n);
+struct Gt;
+void launch_fe_verdicts(const Gt* fe, int n, int32_t* codes, hipStream_t s);
+// ---- checks that each carry their own message (bn256_msgs.hip)
+static constexpr int kG1TabWindows = 64, kG1TabDigits = 15;  // 4-bit windows of a 256-bit scalar
+static constexpr int kG1TabEntries = kG1TabWindows * kG1TabDigits;
+// tab[15 j + d - 1] = d 16^j G1 (affine), the fixed-base table of launch_hash_points
+void launch_g1_base_table(PointG1* tab, hipStream_t s);
+// hashedMessage's scalar of message i (pool[off[i] .. off[i] + len[i])): k[8 i ..]
+// and hcodes[i] = HG_OK, HG_ERR_HASH_EOF, or HG_ERR_ARG for a range past pool_len
+void launch_hash_scalars(const uint8_t* pool, uint64_t pool_len, const uint32_t* off, const uint32_t* len, int n,
+                         uint32_t* k, int32_t* hcodes, hipStream_t s);
+// out[i] = k_i G1 (affine; infinity for k_i = 0 mod Order); hcodes (optional):
+// where hcodes[i] != HG_OK the scalar is not read and out[i] is the generator
+void launch_hash_points(const uint32_t* k, const int32_t* hcodes, int n, const PointG1* tab, PointG1* out,
+                        hipStream_t s);
+// codes[i] = hcodes[i] where codes[i] is still HG_OK (unmarshal errors come first)
+void launch_merge_hash_codes(const int32_t* hcodes, int n, int32_t* codes, hipStream_t s);
+// launch_verify / launch_verify_split with check i on hpts[i]
+void launch_verify_msgs(const CheckIn* in, int n, const LineCoef* tab, const PointG1* hpts, int32_t* codes,
+                        hipStream_t s);
+bool launch_verify_msgs_split(const CheckIn* in, int n, const LineCoef* tab, const PointG1* hpts, int32_t* codes,
+                              uint8_t* ws, hipStream_t s);
 void launch_pair(const PointG1* g1s, const PointG2* g2s, int n, const LineCoef* tab, uint8_t* gt, hipStream_t s);
 // blocks/block_base: the aligned block sums of the registry (hg_registry_load);
 // level k block j at blocks[block_base[k] + j] for 1 <= k <= levels

@@ -172,6 +172,26 @@ struct CheckCtx {
   bool use_s;   // sig contributes (not infinity)
 };
 
+// the Miller loop's per-check inputs (pk and sig decoded by k_decode_checks);
+// hpt: the check's H (the batch's one point, or its own: bn256_msgs.hip)
+HG_DEV CheckCtx check_ctx(const CheckIn& I, const PointG1* hpt) {
+  CheckCtx C;
+  C.qx = I.pk.x;
+  C.qy = I.pk.y;
+  C.hx = hpt->x;
+  C.hy = hpt->y;
+  C.sx = I.sig.x;
+  C.sy = I.sig.y;
+  C.use_q = I.pk.inf == 0;
+  C.use_s = I.sig.inf == 0;
+  if (!C.use_q) {  // keep the (unused) doubling chain well-defined
+    const Fp2 gx = HG_G2X, gy = HG_G2Y;
+    C.qx = gx;
+    C.qy = gy;
+  }
+  return C;
+}
+
 // Writes the team's G2 register file: point R = Q (projective, see below), Q, -Qy, the
 // Frobenius images q1 = pi(Q), -q2 = (Qx gamma2[2], Qy) (optate.go miller),
 // the G1 points and constants. has_fixed && C.use_s: the G2Base pairing at

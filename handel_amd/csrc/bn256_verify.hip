@@ -15,25 +15,6 @@ __device__ uint64_t g_diag[4096 * 16];
 #endif
 
 
-// the Miller loop's per-check inputs (pk and sig decoded by k_decode_checks)
-HG_DEV CheckCtx check_ctx(const CheckIn& I, const PointG1* hpt) {
-  CheckCtx C;
-  C.qx = I.pk.x;
-  C.qy = I.pk.y;
-  C.hx = hpt->x;
-  C.hy = hpt->y;
-  C.sx = I.sig.x;
-  C.sy = I.sig.y;
-  C.use_q = I.pk.inf == 0;
-  C.use_s = I.sig.inf == 0;
-  if (!C.use_q) {  // keep the (unused) doubling chain well-defined
-    const Fp2 gx = HG_G2X, gy = HG_G2Y;
-    C.qx = gx;
-    C.qy = gy;
-  }
-  return C;
-}
-
 // TEAMS checks per workgroup of 16 * TEAMS lanes (one wave; LDS sized to TEAMS)
 template <int TEAMS>
 __global__ __launch_bounds__(64) void k_verify(const CheckIn* in, int n, const LineCoef* tab,
@@ -119,8 +100,13 @@ __global__ __launch_bounds__(256) void k_fe_verdicts(const Gt* fe, int n, int32_
 }
 
 // the Miller values, then (256-byte aligned) launch_fe12's workspace
-static size_t fe_bytes(int n) { return ((size_t)n * sizeof(Gt) + 255) / 256 * 256; }
+size_t verify_split_fe_bytes(int n) { return ((size_t)n * sizeof(Gt) + 255) / 256 * 256; }
+static size_t fe_bytes(int n) { return verify_split_fe_bytes(n); }
 size_t verify_split_ws_bytes(int n) { return fe_bytes(n) + fe12_ws_bytes(n); }
+// k_fe_verdicts for the split form's other Miller kernel (bn256_msgs.hip)
+void launch_fe_verdicts(const Gt* fe, int n, int32_t* codes, hipStream_t s) {
+  if (n > 0) k_fe_verdicts<<<nblk(n, 256), 256, 0, s>>>(fe, n, codes);
+}
 
 // false (nothing launched, the codes untouched) above kSig12MaxN, which
 // verify_split_for (bn256_sigform.h) never sends here

@@ -1,8 +1,9 @@
 // hg_api.cpp — host side of the C ABI declared in include/handel_gpu.h: the
 // context's lifetime, the message, the registry and the single-check calls.
 // Aggregate verification, its GT tables and the service lanes are in
-// hg_aggregate.cpp, packet intake and the stores in hg_intake.cpp; the state
-// they share is hg_ctx.h.
+// hg_aggregate.cpp, packet intake and the stores in hg_intake.cpp, the batches
+// whose checks each carry their own message in hg_msgs.cpp; the state they
+// share is hg_ctx.h.
 //
 // Mirrors the reference's call structure:
 //   Constructor / G2Base           -> hg_create (+ the G2Base line table)
@@ -570,6 +571,7 @@ size_t hg_context_bytes(hg_ctx* c) {
   b += c->ws.bytes();
   for (const hg_lane* l : c->lanes) b += l->bytes();
   b += c->sub_count.bytes() + c->pkts.bytes();
+  b += c->msgs.bytes();  // nothing until the first multi-message call (it builds the G1 base table)
   return b;
 }
 

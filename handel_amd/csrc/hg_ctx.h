@@ -2,8 +2,8 @@
 // (hg_ctx, hg_lane, hg_stores) and what every host file of the C ABI shares:
 // the submission chain, phase timing, error reporting. Internal: hg_api.cpp
 // (context, message, registry, single checks), hg_aggregate.cpp (GT tables,
-// aggregate verification, lanes) and hg_intake.cpp (packets, stores) include
-// it. Every device resource below is held by an owner of hg_dev.h, so
+// aggregate verification, lanes), hg_intake.cpp (packets, stores) and
+// hg_msgs.cpp (checks on their own messages) include it. Every device resource below is held by an owner of hg_dev.h, so
 // deleting a context, a lane or a store set frees what it holds.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,6 +56,21 @@ struct Ws {
     return pts2.bytes() + pts1.bytes() + checks.bytes() + codes_b.bytes() + codes_c.bytes() + order.bytes() +
            agg_ws.bytes() + gt_plan.bytes() + gt_hdr.bytes() + gt_terms.bytes() + gt_ord.bytes() + gt_multi.bytes() +
            gt_partial.bytes() + gt_y.bytes() + gt_fe.bytes() + sig_lines.bytes();
+  }
+};
+
+// Batches whose checks each carry their own message (hg_msgs.cpp): the G1 base
+// table (empty until the context's first such call builds it) and the calls'
+// workspaces, shared like the others under the context's submission chain.
+struct MsgWs {
+  DevBuf<PointG1> g1_tab;    // kG1TabEntries: d 16^j G1
+  DevBuf<uint32_t> k;        // hashedMessage's scalar, 8 words per check
+  DevBuf<int32_t> hcodes;    // HG_OK / HG_ERR_HASH_EOF / HG_ERR_ARG per check
+  DevBuf<PointG1> h;         // H per check
+  DevBuf<uint8_t> pool;      // the host variants' staging: messages,
+  DevBuf<uint32_t> off, len; // their offsets and lengths
+  size_t bytes() const {
+    return g1_tab.bytes() + k.bytes() + hcodes.bytes() + h.bytes() + pool.bytes() + off.bytes() + len.bytes();
   }
 };
 
@@ -130,6 +145,7 @@ struct hg_ctx {
   DevBuf<hg_request> reqs;
   DevBuf<hg_packet> pkts;  // hg_parse_packets staging
   DevBuf<uint64_t> words;
+  MsgWs msgs;  // hg_verify_batch_msgs*, hg_hash_messages
   // -1: the volume policy; 0..2: every aggregate submission at that level
   // (hg_set_aggregate_level; HG_GT_LEVEL / HG_AGG_PATH give the default)
   int pinned_level = -1;

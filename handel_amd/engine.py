@@ -183,6 +183,84 @@ class Engine:
         self._check(self.L.hg_verify_batch_device(self.ctx, d_pks, d_sigs, n, d_codes, stream or None),
                     "hg_verify_batch_device")
 
+    # ----------------------------------------------------------- checks on their own messages
+    @staticmethod
+    def pack_messages(msgs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(pool, msg_off, msg_len) of hg_verify_batch_msgs: the messages end
+        to end, equal messages stored once."""
+        off = np.zeros(len(msgs), dtype=np.uint32)
+        ln = np.zeros(len(msgs), dtype=np.uint32)
+        seen, parts, at = {}, [], 0
+        for i, m in enumerate(msgs):
+            m = bytes(m)
+            if m not in seen:
+                seen[m] = at
+                parts.append(m)
+                at += len(m)
+            off[i], ln[i] = seen[m], len(m)
+        if at >= 1 << 32:
+            raise ValueError("the messages of one batch must stay below 2^32 bytes")
+        return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), off, ln
+
+    def verify_batch_msgs_pool(self, pool, msg_off, msg_len, pks: bytes, sigs: bytes) -> np.ndarray:
+        """hg_verify_batch_msgs on a caller-built pool: check i's message is
+        pool[msg_off[i] : msg_off[i] + msg_len[i]]."""
+        pool, a, b = _u8(pool), _u8(pks), _u8(sigs)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        ln = np.ascontiguousarray(msg_len, dtype=np.uint32)
+        n = len(b) // 64
+        if len(a) != 128 * n or len(off) != n or len(ln) != n:
+            raise ValueError("one message range, 128 key bytes and 64 signature bytes per check")
+        codes = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.L.hg_verify_batch_msgs(self.ctx, _ptr(pool) if len(pool) else None, len(pool), _ptr(off),
+                                                    _ptr(ln), _ptr(a), _ptr(b), n, _ptr(codes)),
+                        "hg_verify_batch_msgs")
+        return codes
+
+    def verify_batch_msgs(self, msgs: Sequence[bytes], pks: bytes, sigs: bytes) -> np.ndarray:
+        """PublicKey.VerifySignature(msgs[i], sigs[i]) for n checks that each
+        carry their own message, in one batch (hg_verify_batch_msgs); the
+        context's current message and tables stay as they are."""
+        pool, off, ln = self.pack_messages(msgs)
+        return self.verify_batch_msgs_pool(pool, off, ln, pks, sigs)
+
+    def verify_batch_msgs_device(self, d_pool: int, pool_len: int, d_msg_off: int, d_msg_len: int, d_pks: int,
+                                 d_sigs: int, n: int, d_codes: int, stream: int = 0) -> None:
+        """hg_verify_batch_msgs_device on raw device pointers (asynchronous); a
+        range past pool_len gives that check HG_ERR_ARG."""
+        self._check(self.L.hg_verify_batch_msgs_device(self.ctx, d_pool or None, pool_len, d_msg_off, d_msg_len, d_pks,
+                                                       d_sigs, n, d_codes, stream or None),
+                    "hg_verify_batch_msgs_device")
+
+    def hash_messages(self, msgs: Sequence[bytes]) -> Tuple[bytes, np.ndarray]:
+        """hashedMessage x n (hg_hash_messages): (n x 64 bytes of G1 marshals,
+        codes); an HG_ERR_HASH_EOF entry holds the generator as a placeholder."""
+        pool, off, ln = self.pack_messages(msgs)
+        return self.hash_messages_pool(pool, off, ln)
+
+    def hash_messages_pool(self, pool, msg_off, msg_len) -> Tuple[bytes, np.ndarray]:
+        pool = _u8(pool)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        ln = np.ascontiguousarray(msg_len, dtype=np.uint32)
+        n = len(off)
+        out = np.zeros(n * 64, dtype=np.uint8)
+        codes = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.L.hg_hash_messages(self.ctx, _ptr(pool) if len(pool) else None, len(pool), _ptr(off),
+                                                _ptr(ln), n, _ptr(out), _ptr(codes)), "hg_hash_messages")
+        return out.tobytes(), codes
+
+    def debug_g1_base_mul(self, scalars: Sequence[int]) -> bytes:
+        """k * G1 marshals by the fixed-base kernel alone (hg_debug_g1_base_mul)."""
+        n = len(scalars)
+        k = np.array([[(int(s) >> (32 * w)) & 0xFFFFFFFF for w in range(8)] for s in scalars],
+                     dtype=np.uint32).reshape(n, 8)
+        out = np.zeros(n * 64, dtype=np.uint8)
+        if n:
+            self._check(self.L.hg_debug_g1_base_mul(self.ctx, _ptr(k), n, _ptr(out)), "hg_debug_g1_base_mul")
+        return out.tobytes()
+
     def pack_verdicts_device(self, d_codes: int, n: int, d_bits: int, stream: int = 0):
         """Device verdict bitset (hg_pack_verdicts_device): ceil(n/8) bytes,
         bit j of byte b = check 8b+j passed."""

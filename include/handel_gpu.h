@@ -131,6 +131,46 @@ int hg_verify_batch(hg_ctx* ctx, const uint8_t* pks, const uint8_t* sigs, size_t
 int hg_verify_batch_device(hg_ctx* ctx, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n, int32_t* d_codes,
                            void* stream);
 
+/* n independent PublicKey.VerifySignature(msg_i, sig_i) checks, EACH ON ITS
+ * OWN MESSAGE (bn256/go/bn256.go:82-94: the message is an argument of every
+ * call). Message i is pool[msg_off[i] .. msg_off[i] + msg_len[i]): any
+ * alignment, any length (0 included), messages may share or repeat bytes.
+ * hashedMessage (bn256/go/bn256.go:210-218) runs for every check on the device.
+ * Per-check precedence is the reference's: the unmarshal error of pk, then of
+ * sig (parsed before VerifySignature is called), HG_ERR_HASH_EOF (about 44 %
+ * of arbitrary messages: digest 0 or >= Order), then the pairing verdict.
+ * Every (off, len) is checked against pool_len before anything is launched:
+ * a range past the pool, or pool_len >= 2^32, is HG_ERR_ARG for the call
+ * (hg_last_error names the check). n = 0 is HG_OK. The call neither reads nor
+ * changes the context's current or cached message, its H, its GT tables or
+ * their level, and needs no hg_set_message and no registry. */
+int hg_verify_batch_msgs(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                         const uint32_t* msg_len, const uint8_t* pks, const uint8_t* sigs, size_t n,
+                         int32_t* codes);
+/* Same (bn256/go/bn256.go:82-94) with every buffer resident in device memory;
+ * `stream` is a hipStream_t (NULL = the context's stream). Asynchronous on the
+ * stream, ordered like hg_verify_batch_device. The ranges cannot be checked on
+ * the host: a check whose range leaves the pool reads nothing and gets the
+ * per-check code HG_ERR_ARG (below the unmarshal errors, like the hash's EOF). */
+int hg_verify_batch_msgs_device(hg_ctx* ctx, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
+                                const uint32_t* d_msg_len, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n,
+                                int32_t* d_codes, void* stream);
+/* hashedMessage x n (bn256/go/bn256.go:210-218): h_out[64 i ..] = the G1
+ * marshal of H(msg_i), codes[i] = HG_OK; or HG_ERR_HASH_EOF, the 64 bytes then
+ * being the generator's marshal (a placeholder). Arguments as
+ * hg_verify_batch_msgs. */
+int hg_hash_messages(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                     const uint32_t* msg_len, size_t n, uint8_t* h_out, int32_t* codes);
+/* Probe of the fixed-base multiplication behind hashedMessage's
+ * new(bn256.G1).ScalarBaseMult(k) (bn256/go/bn256.go:217): out[64 i ..] = the
+ * G1 marshal of k_i * G1 for n scalars of 8 little-endian 32-bit words (any
+ * 256-bit value; zeros for a multiple of Order). */
+int hg_debug_g1_base_mul(hg_ctx* ctx, const uint32_t* k_words, size_t n, uint8_t* out);
+/* hashedMessage's scalar alone, on the host (no context, no GPU): SHA-256 and
+ * the crypto/rand.Int(reader, Order) rule (bn256/go/bn256.go:210-216) by the
+ * code the device runs. k: 8 little-endian words. HG_OK or HG_ERR_HASH_EOF. */
+int hg_debug_hash_scalar(const uint8_t* msg, size_t len, uint32_t k[8]);
+
 /* Verdict bitset of n device-resident codes: bit j of byte b (LSB first) = 1
  * iff check 8b+j returned HG_OK; ceil(n/8) bytes, tail bits 0. Replaces the
  * per-check `err == nil` branch of verifyAndPublish (processing.go:270-287)
