@@ -273,21 +273,9 @@ func (e *Engine) VerifyBatchMsgs(msgs [][]byte, pks, sigs []byte) ([]int32, erro
 	if n == 0 {
 		return nil, nil
 	}
-	off := make([]uint32, n)
-	ln := make([]uint32, n)
-	seen := map[string]uint32{}
-	var pool []byte
-	for i, m := range msgs {
-		at, ok := seen[string(m)]
-		if !ok {
-			if uint64(len(pool))+uint64(len(m)) >= 1<<32 {
-				return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyBatchMsgs: messages above 4 GiB"}
-			}
-			at = uint32(len(pool))
-			seen[string(m)] = at
-			pool = append(pool, m...)
-		}
-		off[i], ln[i] = at, uint32(len(m))
+	pool, off, ln, err := packMessages("VerifyBatchMsgs", msgs)
+	if err != nil {
+		return nil, err
 	}
 	codes := failedCodes(n)
 	rc := C.hg_verify_batch_msgs(e.ctx, bytePtr(pool), C.size_t(len(pool)), (*C.uint32_t)(unsafe.Pointer(&off[0])),
@@ -423,6 +411,70 @@ func (e *Engine) VerifyMultiSignatures(msg []byte, bitLens []int, words [][]uint
 		if bitLens[i] != size {
 			codes[i] = C.HG_ERR_MULTI_SIZES
 		}
+	}
+	return codes, nil
+}
+
+// packMessages lays msgs end to end (equal messages, compared as strings,
+// stored once): the pool, msg_off and msg_len of the hg_*_msgs calls.
+func packMessages(who string, msgs [][]byte) (pool []byte, off, ln []uint32, err error) {
+	off = make([]uint32, len(msgs))
+	ln = make([]uint32, len(msgs))
+	seen := map[string]uint32{}
+	for i, m := range msgs {
+		at, ok := seen[string(m)]
+		if !ok {
+			if uint64(len(pool))+uint64(len(m)) >= 1<<32 {
+				return nil, nil, nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: who + ": messages above 4 GiB"}
+			}
+			at = uint32(len(pool))
+			seen[string(m)] = at
+			pool = append(pool, m...)
+		}
+		off[i], ln[i] = at, uint32(len(m))
+	}
+	return pool, off, ln, nil
+}
+
+// VerifyMultiSignaturesMsgs is crypto.go:120-137 VerifyMultiSignature(msgs[i],
+// ms_i, reg, cons) for every (message, bitset, signature) triple in one launch
+// (hg_verify_multisig_msgs): a node catching up on many rounds, each round with
+// its own message. bitLens[i] must equal the registry size, or the request
+// fails with "verify multisignature: inconsistent sizes". hashedMessage runs
+// per request on the device; the context's current message and its tables stay
+// as they are.
+func (e *Engine) VerifyMultiSignaturesMsgs(msgs [][]byte, bitLens []int, words [][]uint64, sigs []byte) ([]int32, error) {
+	n := len(msgs)
+	if len(bitLens) != n || len(words) != n || len(sigs) != 64*n {
+		return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyMultiSignaturesMsgs: sizes"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	pool, off, ln, err := packMessages("VerifyMultiSignaturesMsgs", msgs)
+	if err != nil {
+		return nil, err
+	}
+	size := int(C.hg_registry_size(e.ctx))
+	lens := make([]uint32, n)
+	woff := make([]uint32, n)
+	var all []uint64
+	for i := range lens {
+		if bitLens[i] < 0 || bitLens[i] > math.MaxUint32 || len(words[i]) < (bitLens[i]+63)/64 {
+			return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: fmt.Sprintf("multisignature %d: malformed bitset", i)}
+		}
+		lens[i], woff[i] = uint32(bitLens[i]), uint32(len(all))
+		if bitLens[i] == size { // any other length fails the size check; its words are never read
+			all = append(all, words[i][:(bitLens[i]+63)/64]...)
+		}
+	}
+	codes := failedCodes(n)
+	rc := C.hg_verify_multisig_msgs(e.ctx, bytePtr(pool), C.size_t(len(pool)), (*C.uint32_t)(unsafe.Pointer(&off[0])),
+		(*C.uint32_t)(unsafe.Pointer(&ln[0])), (*C.uint32_t)(unsafe.Pointer(&lens[0])),
+		(*C.uint32_t)(unsafe.Pointer(&woff[0])), C.size_t(n), wordPtr(all), C.size_t(len(all)), bytePtr(sigs),
+		codePtr(codes))
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
 	}
 	return codes, nil
 }

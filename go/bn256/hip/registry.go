@@ -242,3 +242,56 @@ func (r *Registry) VerifyMultiSignatures(msg []byte, ms []*handel.MultiSignature
 	}
 	return out
 }
+
+// VerifyMultiSignaturesMsgs is crypto.go:120-137 VerifyMultiSignature(msgs[i],
+// ms[i], reg, cons) for many multisignatures over this registry in one launch,
+// each on its own message (hg_verify_multisig_msgs): the final signatures of
+// many rounds, checked later by a node catching up, a monitor or a bridge.
+// Each error is the reference's: "verify multisignature: inconsistent sizes"
+// or the VerifySignature error. The engine's current message is not used.
+func (r *Registry) VerifyMultiSignaturesMsgs(msgs [][]byte, ms []*handel.MultiSignature) []error {
+	out := make([]error, len(ms))
+	if len(msgs) != len(ms) {
+		for i := range out {
+			out[i] = errors.New("hip: one message per multisignature")
+		}
+		return out
+	}
+	r.e.regMu.RLock()
+	defer r.e.regMu.RUnlock()
+	if !r.current() {
+		for i := range out {
+			out[i] = errors.New("hip: registry is no longer loaded on its engine")
+		}
+		return out
+	}
+	kept := make([][]byte, 0, len(ms))
+	lens := make([]int, 0, len(ms))
+	words := make([][]uint64, 0, len(ms))
+	sigs := make([]byte, 0, 64*len(ms))
+	where := make([]int, 0, len(ms))
+	for i, m := range ms {
+		s, err := m.Signature.(*SigBLS).MarshalBinary()
+		if err != nil {
+			out[i] = err
+			continue
+		}
+		kept = append(kept, msgs[i])
+		lens = append(lens, m.BitSet.BitLength())
+		words = append(words, bitsetWords(m.BitSet))
+		sigs = append(sigs, s...)
+		where = append(where, i)
+	}
+	if len(where) == 0 {
+		return out
+	}
+	codes, err := r.e.VerifyMultiSignaturesMsgs(kept, lens, words, sigs)
+	for j, i := range where {
+		if err != nil {
+			out[i] = err
+		} else {
+			out[i] = r.e.CodeError(codes[j])
+		}
+	}
+	return out
+}

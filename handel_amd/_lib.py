@@ -102,6 +102,9 @@ SIGNATURES = {
     "hg_verify_aggregate_device_bits": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     "hg_verify_aggregate_msg": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P]),
     "hg_verify_multisig": (_I, [_P, _P, _P, _SZ, _P, _SZ, _P, _P]),
+    "hg_verify_aggregate_msgs": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _P]),
+    "hg_verify_aggregate_msgs_device": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P, _P]),
+    "hg_verify_multisig_msgs": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P]),
     "hg_aggregate_pk": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "hg_combine_g1": (_I, [_P, _P, _P, _SZ, _P, _P]),
     "hg_combine_g2": (_I, [_P, _P, _P, _SZ, _P, _P]),

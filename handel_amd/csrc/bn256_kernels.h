@@ -77,6 +77,14 @@ void launch_verify_msgs(const CheckIn* in, int n, const LineCoef* tab, const Poi
                         hipStream_t s);
 bool launch_verify_msgs_split(const CheckIn* in, int n, const LineCoef* tab, const PointG1* hpts, int32_t* codes,
                               uint8_t* ws, hipStream_t s);
+// ---- aggregate requests that each carry their own message (bn256_aggmsgs.hip)
+// lvl[i] = HG_OK or HG_ERR_LEVEL (processing.go:350-352), launch_aggregate's codes in
+void launch_aggmsgs_levels(const AggRequest* reqs, int n, uint32_t nreg, int32_t* lvl, hipStream_t s);
+// after launch_aggregate(..., in, lvl): in[i].sig = the decoded signature and
+// codes[i] = unmarshal error > HG_ERR_LEVEL > hcodes[i] > HG_ERR_EMPTY_AGG > HG_OK;
+// in[i].pk becomes infinity where lvl[i] is HG_ERR_LEVEL
+void launch_aggmsgs_merge(const uint8_t* sigs, int n, int flavor, const int32_t* lvl, const int32_t* hcodes,
+                          CheckIn* in, int32_t* codes, hipStream_t s);
 void launch_pair(const PointG1* g1s, const PointG2* g2s, int n, const LineCoef* tab, uint8_t* gt, hipStream_t s);
 // blocks/block_base: the aligned block sums of the registry (hg_registry_load);
 // level k block j at blocks[block_base[k] + j] for 1 <= k <= levels

@@ -1,11 +1,14 @@
 // hg_msgs.cpp — the C ABI's batches whose checks each carry their own message
 // (include/handel_gpu.h: hg_verify_batch_msgs*, hg_hash_messages and the two
-// probes). The reference's PublicKey.VerifySignature takes the message per
+// probes) and whose aggregate requests do (hg_verify_aggregate_msgs*,
+// hg_verify_multisig_msgs: VerifyMultiSignature(msg, ...), crypto.go:120-137).
+// The reference's PublicKey.VerifySignature takes the message per
 // call (bn256/go/bn256.go:82-94); here hashedMessage (bn256/go/bn256.go:210-218)
 // runs for every check on the device (bn256_msgs.hip) and the pairing kernels
 // read H per check. Nothing below touches the context's messages (hg_ctx::cur,
 // alt), their H or their GT tables.
 #include <cstdio>
+#include <vector>
 
 #include "hg_ctx.h"
 #include "hg_sha256.h"
@@ -92,7 +95,170 @@ static int stage_messages(hg_ctx* c, const uint8_t* pool, size_t pool_len, const
   return HG_OK;
 }
 
+// ---------------------------------------------------------------- aggregate requests on their own messages
+// hg_verify_aggregate_msgs*: verifySignature (processing.go:342-368) and
+// VerifyMultiSignature (crypto.go:120-137) with the message per request. GT
+// tables are e(H, pk_i) for one H, so they cannot serve this path: every batch
+// runs the level-0 flow of hg_aggregate.cpp (flow_g2_or_mixed), the G2 fold and
+// the two-pairing check, with the check reading H per request:
+//   s:    level codes, G2 fold into ws.checks ......... -> wait -> merge -> k_msgs_verify (-> keys out)
+//   side: wait -> k_hash_scalars, k_hash_points -> join
+// The hash depends on nothing the fold produces (one latency-bound chain per
+// wave), so it runs on the workspace's side stream beside the fold;
+// hg_set_fold_overlap(ctx, 0) runs it first on s (same codes, for measuring).
+// The pairing always runs in the one-kernel form here, whatever
+// hg_set_verify_split says: the split form's Miller kernel ran 1.20 ms in
+// bn256_msgs.hip's unit against 0.75 ms for identical code elsewhere, cause not
+// found, so this path does not offer it.
+static int aggregate_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_off,
+                                        const uint32_t* d_len, const hg_request* d_reqs, size_t n,
+                                        const uint64_t* d_words, const uint8_t* d_sigs, int32_t* d_codes,
+                                        uint8_t* d_agg, hipStream_t s) {
+  if (c->nreg == 0) {
+    c->err = "hg_verify_aggregate_msgs: needs a registry";
+    return HG_ERR_ARG;
+  }
+  Ws& ws = c->ws;
+  const bool beside = c->pol.overlap;
+  HG_CHECK(c, ws.checks.ensure(n));
+  HG_CHECK(c, ws.order.ensure(n));
+  HG_CHECK(c, ws.agg_ws.ensure(n * agg_partial_bytes() + agg_fixed_bytes()));
+  HG_CHECK(c, ws.codes_c.ensure(n));
+  if (d_agg) HG_CHECK(c, ws.pts2.ensure(n));
+  if (beside) HG_CHECK(c, ensure_side(ws));
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  PhaseTimer all(c, HG_PHASE_SUBMIT, s);
+  const hipStream_t hs = beside ? ws.side.h : s;
+  if (beside) {
+    HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
+    HG_CHECK(c, hipStreamWaitEvent(hs, ws.ev_fork, 0));
+  }
+  int rc = hash_device_locked(c, d_pool, pool_len, d_off, d_len, n, hs);
+  if (beside) HG_CHECK(c, hipEventRecord(ws.ev_join, hs));
+  if (rc) {
+    if (beside) (void)hipStreamWaitEvent(s, ws.ev_join, 0);  // the submission's end covers the side stream
+    return rc;
+  }
+  launch_aggmsgs_levels(d_reqs, (int)n, (uint32_t)c->nreg, ws.codes_c.p, s);
+  PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
+  launch_aggregate(c->wsum.p, (int)c->nreg, c->blocks.p, c->block_base.data(), c->block_levels, d_reqs, (int)n, d_words,
+                   ws.order.p, ws.agg_ws.p, ws.checks.p, ws.codes_c.p, s);
+  fold.stop();
+  if (beside) HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
+  launch_aggmsgs_merge(d_sigs, (int)n, c->flavor, ws.codes_c.p, c->msgs.hcodes.p, ws.checks.p, d_codes, s);
+  PhaseTimer t(c, HG_PHASE_VERIFY, s);
+  launch_verify_msgs(ws.checks.p, (int)n, c->d_lines.p, c->msgs.h.p, d_codes, s);
+  t.stop();
+  if (d_agg) {
+    launch_extract_pk(ws.checks.p, (int)n, ws.pts2.p, s);
+    launch_encode_g2(ws.pts2.p, (int)n, d_agg, s);
+  }
+  all.stop();
+  rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  return HG_OK;
+}
+
+// the host variants: every argument check before anything is launched, then
+// the batch staged on the context's stream. multisig: the requests are
+// VerifyMultiSignature's ([0, N), crypto.go:125-136), whose size check
+// (crypto.go:121-124) has its own code.
+static int aggregate_msgs_host_locked(hg_ctx* c, const char* who, const uint8_t* pool, size_t pool_len,
+                                      const uint32_t* off, const uint32_t* len, const hg_request* reqs, size_t n,
+                                      const uint64_t* words, size_t nwords, const uint8_t* sigs, int32_t* codes,
+                                      uint8_t* agg_out, bool multisig) {
+  int rc = check_ranges(c, who, pool_len, off, len, n);
+  if (rc) return rc;
+  if (c->nreg == 0) {
+    c->err = std::string(who) + ": needs a registry";
+    return HG_ERR_ARG;
+  }
+  for (size_t i = 0; i < n; i++) {
+    const hg_request& r = reqs[i];
+    const bool level_ok = r.bitlen == r.level_size && (size_t)r.offset + r.bitlen <= c->nreg;
+    if (!level_ok || (size_t)r.word_offset + ((size_t)r.bitlen + 63) / 64 <= nwords) continue;
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s: request %zu (word offset %u, %u bits) leaves the %zu bitset words", who, i,
+             r.word_offset, r.bitlen, nwords);
+    c->err = buf;
+    return HG_ERR_ARG;
+  }
+  HG_CHECK(c, hipSetDevice(c->device));
+  HG_CHECK(c, c->reqs.ensure(n));
+  HG_CHECK(c, c->words.ensure(nwords ? nwords : 1));
+  HG_CHECK(c, c->codes_a.ensure(n));
+  HG_CHECK(c, c->bytes_b.ensure(n * 64));
+  uint8_t* d_agg = nullptr;
+  if (agg_out) {
+    HG_CHECK(c, c->bytes_a.ensure(n * 128));
+    d_agg = c->bytes_a.p;
+  }
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  rc = stage_messages(c, pool, pool_len, off, len, n);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(c->reqs.p, reqs, n * sizeof(hg_request), hipMemcpyHostToDevice, c->stream));
+  if (nwords) HG_CHECK(c, hipMemcpyAsync(c->words.p, words, nwords * 8, hipMemcpyHostToDevice, c->stream));
+  HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, c->stream));
+  rc = aggregate_msgs_device_locked(c, c->msgs.pool.p, pool_len, c->msgs.off.p, c->msgs.len.p, c->reqs.p, n,
+                                    c->words.p, c->bytes_b.p, c->codes_a.p, d_agg, c->stream);
+  if (rc) return rc;
+  if (agg_out) HG_CHECK(c, hipMemcpyAsync(agg_out, d_agg, n * 128, hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, hipMemcpyAsync(codes, c->codes_a.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  if (multisig)
+    for (size_t i = 0; i < n; i++)
+      if (codes[i] == HG_ERR_LEVEL) codes[i] = HG_ERR_MULTI_SIZES;
+  return HG_OK;
+}
+
 extern "C" {
+
+int hg_verify_aggregate_msgs_device(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
+                                    const uint32_t* d_msg_len, const hg_request* d_reqs, size_t n,
+                                    const uint64_t* d_words, const uint8_t* d_sigs, int32_t* d_codes,
+                                    uint8_t* d_agg_pk_out, void* stream) {
+  if (!c || (n && (!d_msg_off || !d_msg_len || !d_reqs || !d_sigs || !d_codes)) || (!d_pool && pool_len) ||
+      n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HG_CHECK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  return aggregate_msgs_device_locked(c, d_pool, pool_len, d_msg_off, d_msg_len, d_reqs, n, d_words, d_sigs, d_codes,
+                                      d_agg_pk_out, s);
+}
+
+int hg_verify_aggregate_msgs(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                             const uint32_t* msg_len, const hg_request* reqs, size_t n, const uint64_t* words,
+                             size_t nwords, const uint8_t* sigs, int32_t* codes, uint8_t* agg_pk_out) {
+  if (!c || (n && (!msg_off || !msg_len || !reqs || !sigs || !codes)) || (!pool && pool_len) || (!words && nwords) ||
+      n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  return aggregate_msgs_host_locked(c, "hg_verify_aggregate_msgs", pool, pool_len, msg_off, msg_len, reqs, n, words,
+                                    nwords, sigs, codes, agg_pk_out, false);
+}
+
+int hg_verify_multisig_msgs(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                            const uint32_t* msg_len, const uint32_t* bitlens, const uint32_t* word_offsets, size_t n,
+                            const uint64_t* words, size_t nwords, const uint8_t* sigs, int32_t* codes) {
+  if (!c || (n && (!msg_off || !msg_len || !bitlens || !word_offsets || !sigs || !codes)) || (!pool && pool_len) ||
+      (!words && nwords) || n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  // crypto.go:121-124: the bitset must span the registry (bitlen != N is the
+  // level error of the request [0, N), renamed); the rest is verifySignature
+  std::vector<hg_request> reqs(n);
+  for (size_t i = 0; i < n; i++) reqs[i] = hg_request{0u, bitlens[i], (uint32_t)c->nreg, word_offsets[i]};
+  return aggregate_msgs_host_locked(c, "hg_verify_multisig_msgs", pool, pool_len, msg_off, msg_len, reqs.data(), n,
+                                    words, nwords, sigs, codes, nullptr, true);
+}
 
 int hg_verify_batch_msgs_device(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
                                 const uint32_t* d_msg_len, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n,

@@ -350,6 +350,67 @@ class Engine:
                                                   len(words), _ptr(s), _ptr(codes)), "hg_verify_multisig")
         return codes
 
+    # ----------------------------------------------------------- aggregates on their own messages
+    def verify_aggregate_msgs_pool(self, pool, msg_off, msg_len, reqs: np.ndarray, words: np.ndarray, sigs: bytes,
+                                   want_agg: bool = False):
+        """hg_verify_aggregate_msgs on a caller-built pool: request i's message
+        is pool[msg_off[i] : msg_off[i] + msg_len[i]]."""
+        pool, s = _u8(pool), _u8(sigs)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        ln = np.ascontiguousarray(msg_len, dtype=np.uint32)
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        n = len(reqs)
+        if len(s) != 64 * n or len(off) != n or len(ln) != n:
+            raise ValueError("one message range and 64 signature bytes per request")
+        codes = np.zeros(n, dtype=np.int32)
+        agg = np.zeros(n * 128, dtype=np.uint8) if want_agg else None
+        if n:
+            self._check(self.L.hg_verify_aggregate_msgs(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                        _ptr(off), _ptr(ln), _ptr(reqs), n,
+                                                        _ptr(words) if len(words) else None, len(words), _ptr(s),
+                                                        _ptr(codes), _ptr(agg)),
+                        "hg_verify_aggregate_msgs")
+        return (codes, agg.tobytes()) if want_agg else codes
+
+    def verify_aggregate_msgs(self, msgs: Sequence[bytes], reqs: np.ndarray, words: np.ndarray, sigs: bytes,
+                              want_agg: bool = False):
+        """verify_aggregate for n requests that each carry their own message,
+        in one batch (hg_verify_aggregate_msgs); the context's current message
+        and tables stay as they are."""
+        pool, off, ln = self.pack_messages(msgs)
+        return self.verify_aggregate_msgs_pool(pool, off, ln, reqs, words, sigs, want_agg)
+
+    def verify_aggregate_msgs_device(self, d_pool: int, pool_len: int, d_msg_off: int, d_msg_len: int, d_reqs: int,
+                                     n: int, d_words: int, d_sigs: int, d_codes: int, d_agg: int = 0,
+                                     stream: int = 0) -> None:
+        """hg_verify_aggregate_msgs_device on raw device pointers (asynchronous);
+        a message range past pool_len gives that request HG_ERR_ARG."""
+        self._check(self.L.hg_verify_aggregate_msgs_device(self.ctx, d_pool or None, pool_len, d_msg_off, d_msg_len,
+                                                           d_reqs, n, d_words or None, d_sigs, d_codes, d_agg or None,
+                                                           stream or None),
+                    "hg_verify_aggregate_msgs_device")
+
+    def verify_multisig_msgs(self, msgs: Sequence[bytes], bitlens, word_offsets, words: np.ndarray,
+                             sigs: bytes) -> np.ndarray:
+        """VerifyMultiSignature(msgs[i], ...) (crypto.go:120-137) x n, each on
+        its own message (hg_verify_multisig_msgs)."""
+        pool, off, ln = self.pack_messages(msgs)
+        bl = np.ascontiguousarray(bitlens, dtype=np.uint32)
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint32)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        s = _u8(sigs)
+        n = len(bl)
+        if len(s) != 64 * n or len(off) != n or len(wo) != n:
+            raise ValueError("one message, one word offset and 64 signature bytes per multisignature")
+        codes = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.L.hg_verify_multisig_msgs(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                       _ptr(off), _ptr(ln), _ptr(bl), _ptr(wo), n,
+                                                       _ptr(words) if len(words) else None, len(words), _ptr(s),
+                                                       _ptr(codes)), "hg_verify_multisig_msgs")
+        return codes
+
     def verify_aggregate_device(self, d_reqs: int, n: int, d_words: int, d_sigs: int, d_codes: int,
                                 d_agg: int = 0, stream: int = 0):
         self._check(self.L.hg_verify_aggregate_device(self.ctx, d_reqs, n, d_words, d_sigs, d_codes,

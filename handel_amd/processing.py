@@ -175,3 +175,27 @@ class BatchVerifier:
         if keep:
             codes[np.array(keep)] = self.eng.verify_multisig(bitlens, woffs, allw, bytes(sigs))
         return [None if c == HG_OK else self.eng.code_string(int(c)) for c in codes]
+
+    def verify_multisignatures_msgs(self, items) -> List[Optional[str]]:
+        """VerifyMultiSignature(msg, ms, reg, cons) (crypto.go:120-137) for each
+        (msg, bits, sig) in one GPU batch, every multisignature on its own
+        message (hg_verify_multisig_msgs): a node catching up on many rounds.
+        The verifier's own message is neither used nor changed. Returns None or
+        the reference's error text per entry, as verify_multisignatures."""
+        codes = np.array([sig_length_code(self.eng.flavor_name, bytes(sig)) for _, _, sig in items], dtype=np.int32)
+        keep = [i for i in range(len(items)) if codes[i] == HG_OK]
+        msgs, words, bitlens, woffs, sigs = [], [], [], [], bytearray()
+        nw = 0
+        for i in keep:
+            msg, bits, sig = items[i]
+            w = part.bits_to_words(bits)
+            msgs.append(bytes(msg))
+            words.append(w)
+            bitlens.append(len(bits))
+            woffs.append(nw)
+            nw += len(w)
+            sigs += bytes(sig)[:64]
+        allw = np.concatenate(words) if words else np.zeros(0, dtype=np.uint64)
+        if keep:
+            codes[np.array(keep)] = self.eng.verify_multisig_msgs(msgs, bitlens, woffs, allw, bytes(sigs))
+        return [None if c == HG_OK else self.eng.code_string(int(c)) for c in codes]

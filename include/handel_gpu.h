@@ -199,6 +199,49 @@ int hg_verify_aggregate_msg(hg_ctx* ctx, const uint8_t* msg, size_t len, const h
 int hg_verify_multisig(hg_ctx* ctx, const uint32_t* bitlens, const uint32_t* word_offsets, size_t n,
                        const uint64_t* words, size_t nwords, const uint8_t* sigs, int32_t* codes);
 
+/* n aggregate checks against the registry, EACH ON ITS OWN MESSAGE: request i
+ * is hg_verify_aggregate's request, verified against hashedMessage(msg_i)
+ * (processing.go:342-368 verifySignature; crypto.go:120-137
+ * VerifyMultiSignature(msg, ms, reg, cons) takes the message per call: a node
+ * catching up on many rounds, a monitor, a bridge). Message i is
+ * pool[msg_off[i] .. msg_off[i] + msg_len[i]) as in hg_verify_batch_msgs: any
+ * alignment, any length (0 included), ranges may repeat. Per-request
+ * precedence: the signature's unmarshal error, HG_ERR_LEVEL, HG_ERR_HASH_EOF,
+ * HG_ERR_EMPTY_AGG, the pairing verdict. agg_pk_out (nullable) as
+ * hg_verify_aggregate: the marshal of the aggregate key, zeros for a level
+ * error or an empty bitset; it does not depend on the message. Every message
+ * range is checked against pool_len (which must be below 2^32) and every
+ * request's word range against nwords before anything is launched: a violation
+ * is HG_ERR_ARG for the call and hg_last_error names the request. n = 0 is
+ * HG_OK. GT tables hold e(H, pk_i) for one H and cannot serve this call: every
+ * batch folds the keys in G2 and runs the two-pairing check with H per request
+ * (the path that also serves a go-flavor registry with keys outside G2), the
+ * hash on a side stream beside the fold unless hg_set_fold_overlap(ctx, 0).
+ * The pairing always runs in its one-kernel form, whatever hg_set_verify_split
+ * says. The call needs a registry but no hg_set_message; it neither reads nor
+ * changes the context's current or cached message, their H, the GT tables,
+ * their level or the request count of the table policy. */
+int hg_verify_aggregate_msgs(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                             const uint32_t* msg_len, const hg_request* reqs, size_t n, const uint64_t* words,
+                             size_t nwords, const uint8_t* sigs, int32_t* codes, uint8_t* agg_pk_out);
+/* Same (processing.go:342-368, crypto.go:120-137) with every buffer resident in
+ * device memory; `stream` is a hipStream_t (NULL = the context's stream).
+ * Asynchronous on the stream, ordered like hg_verify_aggregate_device. The
+ * ranges cannot be checked on the host: a request whose message range leaves
+ * the pool reads nothing and gets the per-request code HG_ERR_ARG, in the hash
+ * code's place in the precedence (below the unmarshal and level errors). */
+int hg_verify_aggregate_msgs_device(hg_ctx* ctx, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
+                                    const uint32_t* d_msg_len, const hg_request* d_reqs, size_t n,
+                                    const uint64_t* d_words, const uint8_t* d_sigs, int32_t* d_codes,
+                                    uint8_t* d_agg_pk_out, void* stream);
+/* VerifyMultiSignature(msg_i, ms_i, reg, cons) x n (crypto.go:120-137), each
+ * multisignature on its own message: hg_verify_multisig's requests with
+ * hg_verify_aggregate_msgs's messages and precedence, HG_ERR_MULTI_SIZES
+ * standing where the aggregate form gives HG_ERR_LEVEL. */
+int hg_verify_multisig_msgs(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                            const uint32_t* msg_len, const uint32_t* bitlens, const uint32_t* word_offsets, size_t n,
+                            const uint64_t* words, size_t nwords, const uint8_t* sigs, int32_t* codes);
+
 /* Builds the per-(message, registry) tables of aggregate verification now:
  * e(H, pk_i) for every registry key and the GT products of every 8-key and
  * 16-key window subset and aligned block (bilinearity: e(H, sum pk_i) =
