@@ -300,9 +300,14 @@ __global__ __launch_bounds__(64, 2) void k_sig12_norm(int n, const Gt* fe, SigHa
   sig12_store_terms(T, valid, o, nr, hand + idx, nrm + idx);
 }
 
-// ninv[c] = nrm[c]^-1 (0 for 0: never the case for a Miller value, whose
-// lines all have the coefficient 1 at w^3, so f and its norms are nonzero;
-// guarded so one value cannot spoil the other 255). Per block of 256 checks:
+// ninv[c] = nrm[c]^-1, and 0 for 0. A sig-side Miller value is never zero
+// (its lines all have the coefficient 1 at w^3, so f and its norms are
+// nonzero), but config 2's split form sends the pk-side values of
+// k_verify_ml through k_sig12_norm, and a go-flavor pk of order 13 on the
+// twist has the Miller value 0 (the reference's too: its GT bytes are 384
+// zeros). So the zero guard is live: without it one such key would zero the
+// root and turn the other 255 checks of its block invalid
+// (tests/test_gpu_small_order_keys.py). Per block of 256 checks:
 // a product tree in LDS (8 levels), one fp_inv at the root, the inverses
 // back down (inv(left) = inv(parent) right, inv(right) = inv(parent) left).
 static constexpr int kInvBlock = 256;

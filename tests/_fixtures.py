@@ -88,3 +88,24 @@ def non_g2_points(k: int, seed: int = 1) -> list:
         if q is not None and not O.g2_in_subgroup(q):
             out.append(q)
     return out
+
+
+TWIST_COFACTOR = 2 * O.P - O.ORDER  # #E'(Fp2) = n (2p - n) = n * 13 * 7369 * (a 239-bit rest)
+SMALL_ORDERS = (13, 7369, 95797)
+
+
+def small_order_points(seed: int = 7) -> dict:
+    """{13: T13, 7369: T7369, 95797: T95797}: twist points of exactly these
+    orders (95797 = 13 * 7369), keys x/crypto's G2.Unmarshal accepts like any
+    other point of the twist. A random twist point times n * (cofactor / m)
+    has an order dividing m; a seed that gives infinity for one m is skipped."""
+    while True:
+        q = non_g2_points(1, seed)[0]
+        out = {m: O.g2_mul(q, O.ORDER * (TWIST_COFACTOR // m)) for m in SMALL_ORDERS}
+        if all(t is not None for t in out.values()):
+            break
+        seed += 1
+    for m, t in out.items():
+        assert O.g2_mul(t, m) is None
+    assert O.g2_mul(out[95797], 13) is not None and O.g2_mul(out[95797], 7369) is not None
+    return out

@@ -172,7 +172,12 @@ def fixed_line_eval(sfx=""):
 # addition 3 (x/crypto's Jacobian lineFunctionDouble/Add take 3 and 5). The lines
 # differ from x/crypto's by Fp2 factors and the points are the same points in other
 # coordinates; the final exponentiation removes Fp2 factors, so the pairing (and
-# every verdict) is unchanged for points of the prime-order group.
+# every verdict) is unchanged for points of the prime-order group. The same is
+# checked for twist points outside it that x/crypto's Unmarshal accepts, the
+# small orders 13, 7369 and 95797 included: an order-13 key gives the Miller
+# value 0 here as in x/crypto, the others the reference's pairing
+# (tests/test_small_order_keys.py drives the compiled programs through whole
+# Miller loops, tests/test_gpu_small_order_keys.py the kernels).
 PD = {"XY": "A", "B": "B", "U": "S", "YW": "C", "X2": "G"}            # doubling temporaries
 PA = {"TH": "AB", "LAM": "S1", "D": "D", "C": "I", "K": "S2", "N": "H", "J": "J", "V": "AV", "YL": "L1"}
 
