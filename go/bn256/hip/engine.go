@@ -22,6 +22,7 @@ package hip
 import "C"
 
 import (
+	"crypto/rand"
 	"errors"
 	"fmt"
 	"math"
@@ -356,6 +357,83 @@ func (e *Engine) VerifyAggregate(msg []byte, reqs []Request, wantKeys bool) ([]i
 		return nil, nil, e.fail(rc)
 	}
 	return codes, agg, nil
+}
+
+// DefaultRLCGroup is the group size VerifyAggregateRLC* use for group <= 0
+// (DESIGN.md §3l: the measured choice for batches of thousands of checks).
+const DefaultRLCGroup = 64
+
+// rlcSeed draws the 32 bytes the coefficients of one call derive from. They
+// must not be predictable by whoever sent the signatures, so they come from
+// crypto/rand, fresh for every call, and are never returned.
+func rlcSeed() ([32]byte, error) {
+	var seed [32]byte
+	_, err := rand.Read(seed[:])
+	return seed, err
+}
+
+// VerifyAggregateRLC is VerifyAggregate (verdicts only) on the context's
+// current message (SetMessage / PrepareAggregate) with the pairings of `group`
+// requests at a time replaced by one, under random coefficients
+// (hg_verify_aggregate_rlc): the same code per request (processing.go:342-368
+// verifySignature), except that an invalid signature is accepted with
+// probability at most 2^-64. Groups that fail are verified request by request,
+// so a batch of valid signatures costs about len(reqs)/group pairings. Without
+// GT tables for the message the call runs the exact path. group <= 0 selects
+// DefaultRLCGroup; the largest group is 4096.
+func (e *Engine) VerifyAggregateRLC(reqs []Request, group int) ([]int32, error) {
+	p, err := pack(reqs)
+	if err != nil {
+		return nil, err
+	}
+	if group <= 0 {
+		group = DefaultRLCGroup
+	}
+	seed, err := rlcSeed()
+	if err != nil {
+		return nil, err
+	}
+	codes := failedCodes(len(reqs))
+	var reqPtr *C.hg_request
+	if len(p.reqs) > 0 {
+		reqPtr = &p.reqs[0]
+	}
+	rc := C.hg_verify_aggregate_rlc(e.ctx, reqPtr, C.size_t(len(reqs)), wordPtr(p.words), C.size_t(len(p.words)),
+		bytePtr(p.sigs), (*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint32_t(group), codePtr(codes))
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
+	}
+	return codes, nil
+}
+
+// VerifyAggregateRLCDevice is VerifyAggregateRLC on device-resident requests,
+// bitset words, signatures and codes (hg_verify_aggregate_rlc_device). Unlike
+// the exact device call it synchronises `stream` once: the number of requests
+// in failed groups comes back to the host to size their exact recheck.
+func (e *Engine) VerifyAggregateRLCDevice(dReqs unsafe.Pointer, n int, dWords, dSigs unsafe.Pointer, group int,
+	dCodes, stream unsafe.Pointer) error {
+	if group <= 0 {
+		group = DefaultRLCGroup
+	}
+	seed, err := rlcSeed()
+	if err != nil {
+		return err
+	}
+	rc := C.hg_verify_aggregate_rlc_device(e.ctx, (*C.hg_request)(dReqs), C.size_t(n), (*C.uint64_t)(dWords),
+		(*C.uint8_t)(dSigs), (*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint32_t(group), (*C.int32_t)(dCodes), stream)
+	if rc != C.HG_OK {
+		return e.fail(rc)
+	}
+	return nil
+}
+
+// RLCStats reports the last VerifyAggregateRLC* call: groups checked, groups
+// that failed, requests verified again one by one (hg_rlc_stats). All zero when
+// the exact path ran.
+func (e *Engine) RLCStats() (groups, groupsFailed, rechecked uint64) {
+	var g, f, r C.uint64_t
+	C.hg_rlc_stats(e.ctx, &g, &f, &r)
+	return uint64(g), uint64(f), uint64(r)
 }
 
 // AggregateKeys is the Combine fold alone: the marshalled aggregate public

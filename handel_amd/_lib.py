@@ -105,6 +105,13 @@ SIGNATURES = {
     "hg_verify_aggregate_msgs": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _P]),
     "hg_verify_aggregate_msgs_device": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P, _P]),
     "hg_verify_multisig_msgs": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P]),
+    "hg_verify_aggregate_rlc": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P]),
+    "hg_verify_aggregate_rlc_device": (_I, [_P, _P, _SZ, _P, _P, _P, ctypes.c_uint32, _P, _P]),
+    "hg_rlc_stats": (_I, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                          ctypes.POINTER(ctypes.c_uint64)]),
+    "hg_debug_rlc_coeffs": (_I, [_P, ctypes.c_uint64, _SZ, _P]),
+    "hg_debug_rlc_g1": (_I, [_P, _P, _SZ, _P, ctypes.c_uint32, _P]),
+    "hg_debug_rlc_groups": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "hg_aggregate_pk": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "hg_combine_g1": (_I, [_P, _P, _P, _SZ, _P, _P]),
     "hg_combine_g2": (_I, [_P, _P, _P, _SZ, _P, _P]),

@@ -6,7 +6,7 @@
 // hg_intake.cpp are in hg_ctx.h.
 #include <cstring>
 
-#include "hg_ctx.h"
+#include "hg_aggregate.h"
 
 namespace {
 
@@ -23,7 +23,7 @@ __global__ void k_agg_codes(const int32_t* sig_codes, const int32_t* lvl_codes, 
 }  // namespace
 
 // host-side request validation: the level check of processing.go:350-352
-static void level_codes(hg_ctx* c, const hg_request* reqs, size_t n, std::vector<int32_t>& out) {
+void level_codes(hg_ctx* c, const hg_request* reqs, size_t n, std::vector<int32_t>& out) {
   out.resize(n);
   for (size_t i = 0; i < n; i++) {
     const hg_request& r = reqs[i];
@@ -216,7 +216,7 @@ static int build_fitting_locked(hg_ctx* c, hipStream_t s, int& level) {
 
 // the table level an aggregate submission of n requests runs at (counting
 // them towards the volume policy)
-static int gt_submission_level(hg_ctx* c, size_t n) {
+int gt_submission_level(hg_ctx* c, size_t n) {
   if (c->cur.hash_eof || c->nreg == 0) return 0;
   // a GT level needs the registry's G2 membership (resolved only then)
   const bool wants_gt = c->pinned_level > 0 || c->cur.gt_level > 0 || c->cur.gt_requests + n >= kGtLevel1Requests;
@@ -239,18 +239,12 @@ static int gt_chunk() {
   return chunk;
 }
 static size_t fold_terms_bound(size_t bitlen) { return 8 * ((bitlen + 7 + 63) / 64) + 1; }
-// capacity of a batch's term and chunk lists
-struct FoldCaps {
-  size_t terms = 0, chunks = 0;
-  void add(size_t bitlen) {
-    const size_t m = fold_terms_bound(bitlen);
-    terms += m;
-    chunks += (m + gt_chunk() - 1) / gt_chunk();
-  }
-};
-// device-resident requests: their sizes are unknown on the host, every
-// request is bounded by the registry
-static FoldCaps fold_caps_worst(const hg_ctx* c, size_t n) {
+void FoldCaps::add(size_t bitlen) {
+  const size_t m = fold_terms_bound(bitlen);
+  terms += m;
+  chunks += (m + gt_chunk() - 1) / gt_chunk();
+}
+FoldCaps fold_caps_worst(const hg_ctx* c, size_t n) {
   FoldCaps one;
   one.add(c->nreg);
   return FoldCaps{one.terms * n, one.chunks * n};
@@ -261,15 +255,7 @@ static FoldCaps fold_caps_lane(size_t n, size_t max_words) {
   return FoldCaps{terms, terms / (size_t)gt_chunk() + n};
 }
 
-// The parts of a workspace set a batch of n requests needs, sized in one place
-// for a submission and for a lane (every part it may ever use at its largest
-// batch: a buffer that grew later would be freed and reallocated between
-// batches, and freeing device memory waits for the whole device). Verify: the
-// decoded signatures and their codes; Level: level codes computed here; G2Fold,
-// GtFold (caps): the folds'; AggOut: the aggregate keys; Pairing: the FE values
-// and launch_sig_form's sig_bytes; Side: the side stream and its events.
-enum : unsigned { kWsVerify = 1, kWsLevel = 2, kWsG2Fold = 4, kWsAggOut = 8, kWsGtFold = 16, kWsPairing = 32, kWsSide = 64 };
-static hipError_t ws_ensure(Ws& ws, size_t n, unsigned parts, const FoldCaps& caps = {}, size_t sig_bytes = 0) {
+hipError_t ws_ensure(Ws& ws, size_t n, unsigned parts, const FoldCaps& caps, size_t sig_bytes) {
   hipError_t e = hipSuccess;
   auto grow = [&e](auto& buf, size_t count) {
     if (e == hipSuccess) e = buf.ensure(count);
@@ -313,8 +299,8 @@ static int ensure_gt_fold(hg_ctx* c, Ws& ws, size_t n, const FoldCaps& caps, GtW
 // workspaces that do not fit send this submission to the G2 fold only.
 // may_build = false (service lanes): run at the built level at most; builds
 // happen between batches, with the lanes drained (hg_lane_build_level)
-static int gt_acquire(hg_ctx* c, Ws& ws, hipStream_t s, size_t n, const FoldCaps& caps, int& level, GtWork& w,
-                      bool may_build = true) {
+int gt_acquire(hg_ctx* c, Ws& ws, hipStream_t s, size_t n, const FoldCaps& caps, int& level, GtWork& w,
+               bool may_build) {
   if (!may_build && level > c->cur.gt_level) level = c->cur.gt_level;
   if (level > 0 && c->cur.gt_level < level) {
     int rc = build_fitting_locked(c, s, level);
@@ -345,35 +331,17 @@ __global__ void k_level_codes(const hg_request* r, int n, uint32_t nreg, int32_t
   out[i] = ok ? HG_OK : HG_ERR_LEVEL;
 }
 
-// One batch on the device: n requests, their bitset words and signatures in;
-// codes (and, nullable, agg: the aggregate keys' marshals; bits: the verdict
-// bitset of the codes, hg_pack_verdicts_device's layout) out. lvl (nullable):
-// the level codes, updated in place; computed here when the flow needs them.
-// caps (nullable): the fold's list capacities; else bounded by the registry.
-struct AggBatch {
-  const hg_request* reqs;
-  size_t n;
-  const uint64_t* words;
-  const uint8_t* sigs;
-  int32_t* codes;
-  uint8_t* agg = nullptr;
-  int32_t* lvl = nullptr;
-  uint8_t* bits = nullptr;
-  const FoldCaps* caps = nullptr;
-};
-
-static void gt_prologue(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
+void gt_prologue(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
   launch_agg_prologue(b.reqs, (int)b.n, (uint32_t)c->nreg, b.sigs, c->flavor, ws.pts1.p, b.codes, (int*)gw.hdr,
                       (int)(sizeof(GtHdr) / sizeof(int)), s);
 }
-static void gt_fold(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, int32_t* codes, bool zero_hdr,
-                    hipStream_t s) {
+void gt_fold(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, int32_t* codes, bool zero_hdr, hipStream_t s) {
   launch_gt_fold(b.reqs, (int)b.n, b.words, codes, (int)c->nreg, c->block_levels,
                  gw.win_bits == 16 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, gw, ws.gt_y.p, zero_hdr,
                  s);
 }
 // the pairing in its stored form (the batch's): fe[r] = FE(Miller(G2Base at -sig_r))
-static int pair_stored(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipStream_t s) {
+int pair_stored(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipStream_t s) {
   PhaseTimer t(c, HG_PHASE_VERIFY, s);
   const bool ran = launch_sig_form(form, b.sigs, c->flavor, (int)b.n, c->d_lines.p, ws.sig_lines.p, ws.gt_fe.p, s);
   t.stop();
@@ -384,7 +352,7 @@ static int pair_stored(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipSt
   return HG_OK;
 }
 // the stored FE values against gt_y: the fold's X on a torus set (the verdict bitset with it), else Y
-static void compare_stored(const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
+void compare_stored(const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s) {
   if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.gt_y.p, (int)b.n, b.codes, b.bits, s);
   else if (b.bits) launch_gt_compare_bits(ws.gt_fe.p, ws.gt_y.p, (int)b.n, b.codes, b.bits, s);
   else launch_gt_compare(ws.gt_fe.p, ws.gt_y.p, (int)b.n, b.codes, s);
@@ -433,8 +401,8 @@ static int flow_gt_sequence(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, 
 // The G2 fold (g2_fold: no tables, or the caller wants the aggregate keys'
 // marshals), the GT fold beside it when use_gt, and (verify) the check:
 // k_verify_sig against the GT fold's values, or config 2 on the G2 fold's
-static int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, bool use_gt, bool g2_fold, SigForm form,
-                            const GtWork& gw, hipStream_t s) {
+int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, bool use_gt, bool g2_fold, SigForm form,
+                     const GtWork& gw, hipStream_t s) {
   const int n = (int)b.n;
   int32_t* d_lvl = b.lvl;
   if (!d_lvl) {

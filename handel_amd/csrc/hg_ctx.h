@@ -17,6 +17,7 @@
 
 #include "bn256_gt.h"
 #include "bn256_kernels.h"
+#include "bn256_rlc.h"
 #include "bn256_sigpair.h"
 #include "hg_codes.h"
 #include "hg_dev.h"
@@ -52,10 +53,31 @@ struct Ws {
   // at -sig); launch_verify_split (config 2): the Miller values and the final
   // exponentiation's records
   DevBuf<uint8_t> sig_lines;
+  // random linear combination (hg_rlc.cpp, bn256_rlc.hip): per check the
+  // coefficient and r_i sig_i; per group the live count, the verdict, the G1
+  // sum (point and marshal), the 64 subset products and Z_g; the counters; and,
+  // grown only when a group fails, the recheck's compact arrays
+  DevBuf<uint64_t> rlc_r;
+  DevBuf<RlcJac> rlc_jac;
+  DevBuf<uint32_t> rlc_glive;
+  DevBuf<int32_t> rlc_gcodes;
+  DevBuf<PointG1> rlc_gpts;
+  DevBuf<uint8_t> rlc_gsigs;
+  DevBuf<Gt> rlc_p, rlc_z;
+  DevBuf<RlcHdr> rlc_hdr;
+  DevBuf<uint32_t> rlc_bcount, rlc_idx;
+  DevBuf<uint8_t> rlc_csigs;
+  DevBuf<Gt> rlc_cy;
+  DevBuf<int32_t> rlc_ccodes;
+  size_t rlc_bytes() const {
+    return rlc_r.bytes() + rlc_jac.bytes() + rlc_glive.bytes() + rlc_gcodes.bytes() + rlc_gpts.bytes() +
+           rlc_gsigs.bytes() + rlc_p.bytes() + rlc_z.bytes() + rlc_hdr.bytes() + rlc_bcount.bytes() + rlc_idx.bytes() +
+           rlc_csigs.bytes() + rlc_cy.bytes() + rlc_ccodes.bytes();
+  }
   size_t bytes() const {
     return pts2.bytes() + pts1.bytes() + checks.bytes() + codes_b.bytes() + codes_c.bytes() + order.bytes() +
            agg_ws.bytes() + gt_plan.bytes() + gt_hdr.bytes() + gt_terms.bytes() + gt_ord.bytes() + gt_multi.bytes() +
-           gt_partial.bytes() + gt_y.bytes() + gt_fe.bytes() + sig_lines.bytes();
+           gt_partial.bytes() + gt_y.bytes() + gt_fe.bytes() + sig_lines.bytes() + rlc_bytes();
   }
 };
 
@@ -168,6 +190,8 @@ struct hg_ctx {
   // the context's own aggregate submissions: padded, the two-wave form up to
   // kSigW2MaxN; overlap: hg_set_fold_overlap (HG_GT_OVERLAP=0 gives new contexts false)
   SigPolicy pol;
+  // hg_rlc_stats: the last hg_verify_aggregate_rlc* call's groups checked, groups failed, checks re-verified
+  uint64_t rlc_stats[3] = {0, 0, 0};
   bool verify_split = false;  // hg_set_verify_split; HG_VERIFY_SPLIT=1 gives new contexts true
   // submission order across streams: the event recorded after the last
   // submission and the stream it ran on (the workspaces above are shared)

@@ -1,0 +1,298 @@
+// hg_rlc.cpp — hg_verify_aggregate_rlc*: an aggregate batch whose groups of
+// checks share one pairing under random coefficients (bn256_rlc.hip, DESIGN.md
+// §3l), behind include/handel_gpu.h. The batch runs the prologue and the GT
+// fold of the exact path (hg_aggregate.h), then per group the G1 combination,
+// the shared-squaring multi-exponentiation of the fold values, one pairing and
+// the comparison; the live members of a group that fails go through the exact
+// path's stored pairing and comparison. A context that would not take a GT flow
+// runs the exact path's table-less flow instead.
+#include <cstring>
+
+#include "hg_aggregate.h"
+
+namespace {
+
+struct RlcCall {
+  const uint8_t* seed;       // 32 bytes, or
+  const uint64_t* d_coeffs;  // the probes' coefficients (device)
+  uint32_t group;
+  bool recheck;  // false: hg_debug_rlc_groups stops after the group comparison
+};
+
+hipError_t rlc_ensure(Ws& ws, size_t n, size_t ng) {
+  hipError_t e = hipSuccess;
+  auto grow = [&e](auto& buf, size_t count) {
+    if (e == hipSuccess) e = buf.ensure(count);
+  };
+  grow(ws.rlc_r, n), grow(ws.rlc_jac, n);
+  grow(ws.rlc_glive, ng), grow(ws.rlc_gcodes, ng), grow(ws.rlc_gpts, ng), grow(ws.rlc_gsigs, ng * 64);
+  grow(ws.rlc_p, ng * kRlcBits), grow(ws.rlc_z, ng), grow(ws.rlc_hdr, 1);
+  return e;
+}
+
+RlcSeed seed_of(const uint8_t* seed) {
+  RlcSeed sd{};
+  if (seed) memcpy(sd.b, seed, 32);
+  return sd;
+}
+
+// the G1 side's second half: per group the marshal of sum r_i sig_i over the checks whose code is HG_OK
+void rlc_g1_sum(Ws& ws, const int32_t* codes, size_t n, uint32_t group, size_t ng, hipStream_t s) {
+  launch_rlc_g1_sum(ws.rlc_jac.p, codes, (int)n, group, (int)ng, ws.rlc_gpts.p, ws.rlc_glive.p, s);
+  launch_encode_g1(ws.rlc_gpts.p, (int)ng, ws.rlc_gsigs.p, s);
+}
+
+// The failed groups' live members through the exact check: gathered in index
+// order, paired and compared as a batch of their own, the codes scattered back.
+int rlc_recheck(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, uint32_t group, size_t m, hipStream_t s) {
+  const size_t n = b.n;
+  const SigForm form = sig_form(sig_env(), c->pol, m);
+  HG_CHECK(c, ws.rlc_bcount.ensure((n + 255) / 256));
+  HG_CHECK(c, ws.rlc_idx.ensure(m));
+  HG_CHECK(c, ws.rlc_csigs.ensure(m * 64));
+  HG_CHECK(c, ws.rlc_cy.ensure(m));
+  HG_CHECK(c, ws.rlc_ccodes.ensure(m));
+  HG_CHECK(c, ws.sig_lines.ensure(sig_form_ws_bytes(form, (int)m)));
+  launch_rlc_gather(b.codes, ws.rlc_gcodes.p, (int)n, group, b.sigs, ws.gt_y.p, ws.rlc_bcount.p, ws.rlc_idx.p,
+                    ws.rlc_csigs.p, ws.rlc_cy.p, ws.rlc_ccodes.p, s);
+  const AggBatch cb{nullptr, m, nullptr, ws.rlc_csigs.p, ws.rlc_ccodes.p};
+  int rc = pair_stored(c, cb, ws, form, s);
+  if (rc) return rc;
+  if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.rlc_cy.p, (int)m, ws.rlc_ccodes.p, nullptr, s);
+  else launch_gt_compare(ws.gt_fe.p, ws.rlc_cy.p, (int)m, ws.rlc_ccodes.p, s);
+  launch_rlc_scatter(ws.rlc_idx.p, ws.rlc_ccodes.p, (int)m, b.codes, s);
+  return HG_OK;
+}
+
+// One batch on stream s with the context's workspaces. *ran: the combination
+// ran (false: the exact path did, or nothing for a probe).
+int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* ran, hipStream_t s) {
+  *ran = false;
+  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  if (!c->cur.has_msg) {
+    c->err = "hg_set_message was not called";
+    return HG_ERR_ARG;
+  }
+  const size_t n = b.n, ng = (n + call.group - 1) / call.group;
+  Ws& ws = c->ws;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  int level = gt_submission_level(c, n);
+  GtWork gw{};
+  if (level > 0) {
+    int rc = gt_acquire(c, ws, s, n, b.caps ? *b.caps : fold_caps_worst(c, n), level, gw);
+    if (rc) return rc;
+  }
+  // a set in torus form has one fold table, the 16-key windows
+  if (level > 0 && c->cur.gt_level == 2 && c->cur.torus) level = 2;
+  gw.win_bits = level == 2 ? 16 : 8;
+  gw.torus = level == 2 && c->cur.torus;
+  const SigForm form = sig_form(sig_env(), c->pol, n);
+  if (level == 0) {
+    // no GT flow: the exact path's fold in G2 and two-pairing check
+    if (!call.recheck) {
+      c->err = "hg_debug_rlc_groups: the context has no GT tables to combine over";
+      return HG_ERR_ARG;
+    }
+    HG_CHECK(c, ws_ensure(ws, n, kWsG2Fold | kWsVerify | (b.lvl ? 0 : kWsLevel), {}, sig_form_ws_bytes(form, (int)n)));
+    PhaseTimer all(c, HG_PHASE_SUBMIT, s);
+    int rc = flow_g2_or_mixed(c, b, ws, true, false, true, form, gw, s);
+    if (rc) return rc;
+    all.stop();
+    rc = check_launch(c);
+    if (rc) return rc;
+    HG_CHECK(c, sub.finish());
+    return HG_OK;
+  }
+  const SigForm gform = sig_form(sig_env(), c->pol, ng);
+  // The G1 multiples need the decoded signatures and the coefficients only, so
+  // they run on the side stream beside the fold and the GT stages (a thread's
+  // double-and-add chain is latency no other work of the batch waits for);
+  // hg_set_fold_overlap(ctx, 0) keeps everything on one stream.
+  const bool beside = c->pol.overlap;
+  HG_CHECK(c, ws_ensure(ws, n, kWsVerify | kWsPairing | (beside ? kWsSide : 0), {}, sig_form_ws_bytes(gform, (int)ng)));
+  HG_CHECK(c, rlc_ensure(ws, n, ng));
+  PhaseTimer all(c, HG_PHASE_SUBMIT, s);
+  launch_rlc_prep(seed_of(call.seed), call.d_coeffs, (int)n, (int)ng, ws.rlc_r.p, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
+  gt_prologue(c, b, ws, gw, s);
+  hipStream_t g1s = beside ? (hipStream_t)ws.side : s;
+  if (beside) {
+    HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
+    HG_CHECK(c, hipStreamWaitEvent(ws.side, ws.ev_fork, 0));
+  }
+  launch_rlc_g1_mul(ws.pts1.p, b.codes, ws.rlc_r.p, (int)n, ws.rlc_jac.p, g1s);
+  if (beside) HG_CHECK(c, hipEventRecord(ws.ev_join, ws.side));
+  PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
+  gt_fold(c, b, ws, gw, b.codes, false, s);
+  fold.stop();
+  // the combination's GT stages, a second interval of the phase
+  PhaseTimer comb(c, HG_PHASE_AGGREGATE, s);
+  launch_rlc_gt(ws.gt_y.p, b.codes, ws.rlc_r.p, (int)n, call.group, (int)ng, ws.rlc_p.p, ws.rlc_z.p, s);
+  comb.stop();
+  if (beside) HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
+  rlc_g1_sum(ws, b.codes, n, call.group, ng, s);
+  const AggBatch gb{nullptr, ng, nullptr, ws.rlc_gsigs.p, ws.rlc_gcodes.p};
+  int rc = pair_stored(c, gb, ws, gform, s);
+  if (rc) return rc;
+  if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.rlc_z.p, (int)ng, ws.rlc_gcodes.p, nullptr, s);
+  else launch_gt_compare(ws.gt_fe.p, ws.rlc_z.p, (int)ng, ws.rlc_gcodes.p, s);
+  launch_rlc_count(ws.rlc_gcodes.p, ws.rlc_glive.p, (int)ng, ws.rlc_hdr.p, s);
+  rc = check_launch(c);
+  if (rc) return rc;
+  *ran = true;
+  if (call.recheck) {
+    // the one read-back: how many checks the failed groups hold sizes their launch
+    RlcHdr h{};
+    HG_CHECK(c, hipMemcpyAsync(&h, ws.rlc_hdr.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HG_CHECK(c, hipStreamSynchronize(s));
+    c->rlc_stats[0] = h.groups;
+    c->rlc_stats[1] = h.groups_failed;
+    c->rlc_stats[2] = h.failed_members;
+    if (h.failed_members > n) {
+      c->err = "hg_verify_aggregate_rlc: inconsistent failed-member count";
+      return HG_ERR_DEVICE;
+    }
+    if (h.failed_members) {
+      rc = rlc_recheck(c, b, ws, gw, call.group, h.failed_members, s);
+      if (rc) return rc;
+    }
+  }
+  all.stop();
+  rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, sub.finish());
+  return HG_OK;
+}
+
+// host pointers in, through the context's staging buffers (as hg_verify_aggregate)
+int rlc_host_locked(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
+                    const uint8_t* sigs, const uint64_t* coeffs, const RlcCall& call0, int32_t* codes,
+                    int32_t* group_codes, uint32_t* group_live) {
+  HG_CHECK(c, hipSetDevice(c->device));
+  std::vector<int32_t> lvl;
+  level_codes(c, reqs, n, lvl);
+  FoldCaps caps;  // exact bounds: the host knows every request's size
+  for (size_t i = 0; i < n; i++) {
+    if (lvl[i] != HG_OK) continue;
+    if ((size_t)reqs[i].word_offset + (reqs[i].bitlen + 63) / 64 > nwords) {
+      c->err = "request words out of range";
+      return HG_ERR_ARG;
+    }
+    caps.add(reqs[i].bitlen);
+  }
+  HG_CHECK(c, c->reqs.ensure(n));
+  HG_CHECK(c, c->words.ensure(nwords ? nwords : 1));
+  HG_CHECK(c, c->codes_a.ensure(n));
+  HG_CHECK(c, c->bytes_b.ensure(n * 64));
+  if (coeffs) HG_CHECK(c, c->bytes_a.ensure(n * 8));
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(c->reqs.p, reqs, n * sizeof(hg_request), hipMemcpyHostToDevice, c->stream));
+  if (nwords) HG_CHECK(c, hipMemcpyAsync(c->words.p, words, nwords * 8, hipMemcpyHostToDevice, c->stream));
+  HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, c->stream));
+  if (coeffs) HG_CHECK(c, hipMemcpyAsync(c->bytes_a.p, coeffs, n * 8, hipMemcpyHostToDevice, c->stream));
+  RlcCall call = call0;
+  call.d_coeffs = coeffs ? reinterpret_cast<const uint64_t*>(c->bytes_a.p) : nullptr;
+  const AggBatch b{c->reqs.p, n, c->words.p, c->bytes_b.p, c->codes_a.p, nullptr, nullptr, nullptr, &caps};
+  bool ran = false;
+  int rc = rlc_device_locked(c, b, call, &ran, c->stream);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(codes, c->codes_a.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (group_codes && ran) {
+    const size_t ng = (n + call.group - 1) / call.group;
+    HG_CHECK(c, hipMemcpyAsync(group_codes, c->ws.rlc_gcodes.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
+    HG_CHECK(c, hipMemcpyAsync(group_live, c->ws.rlc_glive.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+
+bool rlc_group_ok(uint32_t group) { return group >= 1 && group <= kRlcMaxGroup; }
+
+}  // namespace
+
+extern "C" {
+
+int hg_verify_aggregate_rlc(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
+                            const uint8_t* sigs, const uint8_t seed[32], uint32_t group, int32_t* codes) {
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!reqs || !sigs || !codes)) || n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  if (n == 0) return HG_OK;
+  return rlc_host_locked(c, reqs, n, words, nwords, sigs, nullptr, RlcCall{seed, nullptr, group, true}, codes, nullptr,
+                         nullptr);
+}
+
+int hg_verify_aggregate_rlc_device(hg_ctx* c, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
+                                   const uint8_t* d_sigs, const uint8_t seed[32], uint32_t group, int32_t* d_codes,
+                                   void* stream) {
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!d_reqs || !d_sigs || !d_codes)) || n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  if (n == 0) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  bool ran = false;
+  return rlc_device_locked(c, AggBatch{d_reqs, n, d_words, d_sigs, d_codes}, RlcCall{seed, nullptr, group, true}, &ran,
+                           s);
+}
+
+int hg_rlc_stats(hg_ctx* c, uint64_t* groups, uint64_t* groups_failed, uint64_t* rechecked) {
+  if (!c) return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (groups) *groups = c->rlc_stats[0];
+  if (groups_failed) *groups_failed = c->rlc_stats[1];
+  if (rechecked) *rechecked = c->rlc_stats[2];
+  return HG_OK;
+}
+
+int hg_debug_rlc_coeffs(const uint8_t seed[32], uint64_t first, size_t n, uint64_t* out) {
+  if (!seed || (n && !out)) return HG_ERR_ARG;
+  for (size_t i = 0; i < n; i++) out[i] = rlc_coeff(seed, first + i);
+  return HG_OK;
+}
+
+int hg_debug_rlc_g1(hg_ctx* c, const uint8_t* sigs, size_t n, const uint64_t* coeffs, uint32_t group,
+                    uint8_t* out64_per_group) {
+  if (!c || !rlc_group_ok(group) || (n && (!sigs || !coeffs || !out64_per_group)) || n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HG_CHECK(c, hipSetDevice(c->device));
+  const size_t ng = (n + group - 1) / group;
+  Ws& ws = c->ws;
+  hipStream_t s = c->stream;
+  HG_CHECK(c, c->bytes_b.ensure(n * 64));
+  HG_CHECK(c, ws_ensure(ws, n, kWsVerify));
+  HG_CHECK(c, rlc_ensure(ws, n, ng));
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, s));
+  HG_CHECK(c, hipMemcpyAsync(ws.rlc_r.p, coeffs, n * 8, hipMemcpyHostToDevice, s));
+  launch_decode_g1(c->bytes_b.p, (int)n, c->flavor, ws.pts1.p, ws.codes_b.p, s);
+  launch_rlc_g1_mul(ws.pts1.p, ws.codes_b.p, ws.rlc_r.p, (int)n, ws.rlc_jac.p, s);
+  rlc_g1_sum(ws, ws.codes_b.p, n, group, ng, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(out64_per_group, ws.rlc_gsigs.p, ng * 64, hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(s));
+  return HG_OK;
+}
+
+int hg_debug_rlc_groups(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
+                        const uint8_t* sigs, const uint64_t* coeffs, uint32_t group, int32_t* codes,
+                        int32_t* group_codes, uint32_t* group_live) {
+  if (!c || !rlc_group_ok(group) || (n && (!reqs || !sigs || !coeffs || !codes || !group_codes || !group_live)) ||
+      n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
+  if (n == 0) return HG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  return rlc_host_locked(c, reqs, n, words, nwords, sigs, coeffs, RlcCall{nullptr, nullptr, group, false}, codes,
+                         group_codes, group_live);
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@ torch tensors) and a HIP stream handle.
 from __future__ import annotations
 
 import ctypes
+import os
 import weakref
 from typing import Optional, Sequence, Tuple
 
@@ -288,6 +289,87 @@ class Engine:
                                                len(words), _ptr(s), _ptr(codes), _ptr(agg)),
                     "hg_verify_aggregate")
         return (codes, agg.tobytes()) if want_agg else codes
+
+    # ------------------------------------------------------------ random linear combination
+    # The default group: profiles/rlc_bench.json (README "Random linear combination")
+    RLC_GROUP = 64
+
+    @staticmethod
+    def _seed(seed: Optional[bytes]) -> np.ndarray:
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        return _u8(seed)
+
+    def verify_aggregate_rlc(self, reqs: np.ndarray, words: np.ndarray, sigs: bytes, seed: Optional[bytes] = None,
+                             group: int = RLC_GROUP) -> np.ndarray:
+        """verify_aggregate with one pairing per `group` checks under random
+        coefficients (hg_verify_aggregate_rlc): the same codes, an invalid
+        signature accepted with probability <= 2^-64 over `seed`, which the
+        signatures' sender must not predict (None: os.urandom(32))."""
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        s = _u8(sigs)
+        sd = self._seed(seed)
+        n = len(reqs)
+        codes = np.zeros(n, dtype=np.int32)
+        self._check(self.L.hg_verify_aggregate_rlc(self.ctx, _ptr(reqs), n, _ptr(words) if len(words) else None,
+                                                   len(words), _ptr(s), _ptr(sd), int(group), _ptr(codes)),
+                    "hg_verify_aggregate_rlc")
+        return codes
+
+    def verify_aggregate_rlc_device(self, d_reqs: int, n: int, d_words: int, d_sigs: int, d_codes: int,
+                                    seed: Optional[bytes] = None, group: int = RLC_GROUP, stream: int = 0):
+        """Device-resident verify_aggregate_rlc; synchronises `stream` once (the
+        failed groups' member count sizes their exact recheck)."""
+        sd = self._seed(seed)
+        self._check(self.L.hg_verify_aggregate_rlc_device(self.ctx, d_reqs, n, d_words, d_sigs, _ptr(sd), int(group),
+                                                          d_codes, stream or None),
+                    "hg_verify_aggregate_rlc_device")
+
+    def rlc_stats(self) -> Tuple[int, int, int]:
+        """The last verify_aggregate_rlc* call: (groups checked, groups that
+        failed, checks re-verified one by one); zeros when the exact path ran."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        self._check(self.L.hg_rlc_stats(self.ctx, *[ctypes.byref(x) for x in v]), "hg_rlc_stats")
+        return tuple(int(x.value) for x in v)
+
+    @staticmethod
+    def debug_rlc_coeffs(seed: bytes, first: int, n: int) -> np.ndarray:
+        """r_first .. r_(first+n-1) by the code the device runs (host only: no context, no GPU)."""
+        out = np.zeros(n, dtype=np.uint64)
+        rc = _lib.load().hg_debug_rlc_coeffs(_ptr(Engine._seed(seed)), int(first), n, _ptr(out))
+        if rc != 0:
+            raise HandelGPUError(f"hg_debug_rlc_coeffs: code {rc}")
+        return out
+
+    def debug_rlc_g1(self, sigs: bytes, coeffs, group: int) -> bytes:
+        """Per group the marshal of sum coeffs[i] sigs[i] (hg_debug_rlc_g1)."""
+        s = _u8(sigs)
+        n = len(s) // 64
+        k = np.ascontiguousarray(np.array([int(c) for c in coeffs], dtype=np.uint64))
+        assert len(k) == n
+        out = np.zeros(((n + group - 1) // group) * 64, dtype=np.uint8)
+        self._check(self.L.hg_debug_rlc_g1(self.ctx, _ptr(s), n, _ptr(k), int(group), _ptr(out)), "hg_debug_rlc_g1")
+        return out.tobytes()
+
+    def debug_rlc_groups(self, reqs: np.ndarray, words: np.ndarray, sigs: bytes, coeffs, group: int):
+        """The combination up to the group comparison with the given coefficients
+        (hg_debug_rlc_groups): (codes, group_codes, group_live)."""
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        s = _u8(sigs)
+        n = len(reqs)
+        k = np.ascontiguousarray(np.array([int(c) for c in coeffs], dtype=np.uint64))
+        assert len(k) == n
+        ng = (n + group - 1) // group
+        codes = np.zeros(n, dtype=np.int32)
+        gcodes = np.zeros(ng, dtype=np.int32)
+        glive = np.zeros(ng, dtype=np.uint32)
+        self._check(self.L.hg_debug_rlc_groups(self.ctx, _ptr(reqs), n, _ptr(words) if len(words) else None,
+                                               len(words), _ptr(s), _ptr(k), int(group), _ptr(codes), _ptr(gcodes),
+                                               _ptr(glive)), "hg_debug_rlc_groups")
+        return codes, gcodes, glive
 
     # ------------------------------------------------------------ packet intake
     def packet_stride_words(self) -> int:

@@ -310,6 +310,53 @@ int hg_verify_aggregate_device(hg_ctx* ctx, const hg_request* d_reqs, size_t n, 
 int hg_verify_aggregate_device_bits(hg_ctx* ctx, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
                                     const uint8_t* d_sigs, int32_t* d_codes, uint8_t* d_bits, void* stream);
 
+/* ---------------------------------------------------------------- random linear combination
+ * hg_verify_aggregate with the pairings of `group` checks at a time replaced by
+ * one. For the checks i of a group, with F_i = prod e(H, pk_j) over check i's
+ * set keys (the GT fold's value),
+ *     e(sum r_i sig_i, G2Base) == prod F_i^(r_i)
+ * holds when every check holds, and with probability <= 2^-64 over the
+ * coefficients when one does not. Codes are hg_verify_aggregate's, check for
+ * check (processing.go:342-368 verifySignature), except that an invalid
+ * signature is accepted with probability <= 2^-64 over `seed`.
+ * seed: 32 bytes the sender of the signatures cannot predict (fresh randomness
+ * per call); r_i = the first 8 bytes, little-endian, of
+ * SHA-256("hg-rlc-v1" || seed || LE64(i)), 0 replaced by 1. group: 1..4096;
+ * groups are the index ranges [g group, (g + 1) group).
+ * The combination runs exactly when hg_verify_aggregate_device would take a GT
+ * flow (a message is set, tables at level 1 or 2: every registry key is then
+ * proven to lie in G2); otherwise the call is the exact path and hg_rlc_stats
+ * reports 0 groups. Checks the prologue and the fold already decided (unmarshal,
+ * level, empty aggregate) keep their code and join no group; a group without a
+ * live member is skipped. The live members of a group whose combined check
+ * fails are verified again one by one, so every code is exact. Sizing that
+ * launch needs the failed groups' member count on the host: each call that runs
+ * the combination synchronises its stream once and reads 16 bytes back (the
+ * count and the statistics), the _device form included. group == 0,
+ * group > 4096 or a NULL seed: HG_ERR_ARG. n = 0: HG_OK. */
+int hg_verify_aggregate_rlc(hg_ctx* ctx, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
+                            const uint8_t* sigs, const uint8_t seed[32], uint32_t group, int32_t* codes);
+int hg_verify_aggregate_rlc_device(hg_ctx* ctx, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
+                                   const uint8_t* d_sigs, const uint8_t seed[32], uint32_t group, int32_t* d_codes,
+                                   void* stream);
+/* last RLC call on this context: groups checked, groups that failed, checks re-verified one by one */
+int hg_rlc_stats(hg_ctx* ctx, uint64_t* groups, uint64_t* groups_failed, uint64_t* rechecked);
+/* r_i for i = first .. first+n-1, on the host, by the code the device runs (no GPU) */
+int hg_debug_rlc_coeffs(const uint8_t seed[32], uint64_t first, size_t n, uint64_t* out);
+/* probes with caller-given coefficients (tests only; never use for verification).
+ * hg_debug_rlc_g1: out64_per_group[64 g ..] = the G1 marshal of sum coeffs[i] sigs[i]
+ * over group g's signatures (zeros for infinity), ceil(n / group) groups; a
+ * signature that does not unmarshal is left out.
+ * hg_debug_rlc_groups: everything up to the group comparison, no recheck:
+ * codes[n] = the prologue's and the fold's codes, group_codes[g] = HG_OK or
+ * HG_ERR_SIG_INVALID, group_live[g] = group g's live members. HG_ERR_ARG when
+ * the context would not run the combination (no GT tables). */
+int hg_debug_rlc_g1(hg_ctx* ctx, const uint8_t* sigs, size_t n, const uint64_t* coeffs, uint32_t group,
+                    uint8_t* out64_per_group);
+int hg_debug_rlc_groups(hg_ctx* ctx, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
+                        const uint8_t* sigs, const uint64_t* coeffs, uint32_t group, int32_t* codes,
+                        int32_t* group_codes, uint32_t* group_live);
+
 /* Batched PublicKey.Combine fold only: n requests -> n*128 B aggregate keys
  * (bn256/go/bn256.go:97-105). codes: HG_OK, HG_ERR_LEVEL or HG_ERR_EMPTY_AGG. */
 int hg_aggregate_pk(hg_ctx* ctx, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
