@@ -18,8 +18,7 @@ __global__ __launch_bounds__(256) void k_aggmsgs_levels(const AggRequest* reqs, 
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const AggRequest r = reqs[i];
-  const bool ok = r.bitlen == r.level_size && (uint64_t)r.offset + r.bitlen <= nreg;
-  lvl[i] = ok ? HG_OK : HG_ERR_LEVEL;
+  lvl[i] = level_ok(r, nreg) ? HG_OK : HG_ERR_LEVEL;
 }
 
 // One thread per request, after the fold has turned lvl[i] into HG_OK,

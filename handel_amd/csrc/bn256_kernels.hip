@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64) void k_decode_g2(const uint8_t* bytes, int n, i
 // n * key != inf (on the twist but outside the order-n subgroup G2). x/crypto's
 // G2.Unmarshal (bn256/go/bn256.go:113-120) accepts such keys; the GT path's
 // bilinearity argument only holds on G2, so a registry holding one is served
-// by the G2 fold + two-pairing check instead (hg_aggregate.cpp gt_max_level).
+// by the G2 fold + two-pairing check instead (hg_gttables.cpp gt_max_level).
 __global__ __launch_bounds__(64) void k_g2_subgroup(const PointG2* reg, int n, int* count) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -114,8 +114,7 @@ __global__ __launch_bounds__(64) void k_agg_prologue(const AggRequest* reqs, int
   int32_t code = decode_g1_one(sigs + (size_t)i * 64, flavor, P);
   pts[i] = P;
   const AggRequest r = reqs[i];
-  const bool level_ok = r.bitlen == r.level_size && (uint64_t)r.offset + r.bitlen <= nreg;
-  if (code == HG_OK && !level_ok) code = HG_ERR_LEVEL;
+  if (code == HG_OK && !level_ok(r, nreg)) code = HG_ERR_LEVEL;
   codes[i] = code;
 }
 
@@ -774,6 +773,16 @@ __global__ __launch_bounds__(64) void k_merge_codes(const int32_t* a, const int3
   // pk decode errors win over sig decode errors (the registry is decoded first)
   out[i] = a[i] != HG_OK ? a[i] : b[i];
 }
+// final = sig decode error > level error > hash EOF > empty aggregate > (verify)
+__global__ void k_agg_codes(const int32_t* sig_codes, const int32_t* lvl_codes, int hash_eof, int n, int32_t* out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int32_t c = sig_codes[i];
+  if (c == HG_OK && lvl_codes[i] == HG_ERR_LEVEL) c = HG_ERR_LEVEL;
+  if (c == HG_OK && hash_eof) c = HG_ERR_HASH_EOF;
+  if (c == HG_OK) c = lvl_codes[i];
+  out[i] = c;
+}
 // Verdict bitset (the one buffer distributed.py gathers across GPUs): bit j of
 // byte b = check 8b + j passed (code 0); one thread per byte, tail bits 0.
 __global__ __launch_bounds__(64) void k_pack_verdicts(const int32_t* codes, int n, uint8_t* bits) {
@@ -883,6 +892,10 @@ void launch_checks_from_points(const PointG2* pks, const PointG1* sigs, int n, C
 }
 void launch_merge_codes(const int32_t* a, const int32_t* b, int n, int32_t* out, hipStream_t s) {
   if (n > 0) k_merge_codes<<<nblk(n, 64), 64, 0, s>>>(a, b, n, out);
+}
+void launch_agg_codes(const int32_t* sig_codes, const int32_t* lvl_codes, int hash_eof, int n, int32_t* out,
+                      hipStream_t s) {
+  if (n > 0) k_agg_codes<<<nblk(n, 256), 256, 0, s>>>(sig_codes, lvl_codes, hash_eof, n, out);
 }
 void launch_pack_verdicts(const int32_t* codes, int n, uint8_t* bits, hipStream_t s) {
   if (n > 0) k_pack_verdicts<<<nblk((n + 7) / 8, 64), 64, 0, s>>>(codes, n, bits);

@@ -1,18 +1,43 @@
-// hg_aggregate.h — the pieces of an aggregate batch (hg_aggregate.cpp) that
-// its random-linear-combination form (hg_rlc.cpp) runs as they are: the table
-// level and fold workspaces of a submission, the prologue, the fold, the stored
-// pairing and its comparison, and the exact path's table-less flow.
+// hg_aggregate.h — the internal interface of aggregate verification: what
+// hg_gttables.cpp (the GT tables), hg_aggregate.cpp (a batch's workspaces, flows,
+// staging and entry points), hg_lanes.cpp (the service lanes), hg_rlc.cpp (the
+// random-linear-combination form) and hg_msgs.cpp (a message per request) use
+// of each other. Every name below has users in at least two of them.
 #pragma once
 #include "hg_ctx.h"
 
+// internal return code: an allocation of the GT path failed (the caller falls back to a lower level)
+static constexpr int kNoMem = -1;
+// an allocation of the GT path: out of device memory -> kNoMem, any other failure -> HG_ERR_DEVICE
+#define HG_GT_ALLOC(ctx, expr)                                                     \
+  do {                                                                             \
+    hipError_t e_ = (expr);                                                        \
+    if (e_ == hipErrorOutOfMemory) {                                               \
+      (void)hipGetLastError(); /* not sticky: keep it out of check_launch */       \
+      return kNoMem;                                                               \
+    }                                                                              \
+    if (e_ != hipSuccess) {                                                        \
+      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);              \
+      return HG_ERR_DEVICE;                                                        \
+    }                                                                              \
+  } while (0)
+
+// ---------------------------------------------------------------- hg_gttables.cpp
+// the table level an aggregate submission of n requests runs at (counting them towards the volume policy)
+int gt_submission_level(hg_ctx* c, size_t n);
+// builds up to `level` on stream s, lowering it (and the context's cap) to what the device and the budget hold
+int build_fitting_locked(hg_ctx* c, hipStream_t s, int& level);
+
+// ---------------------------------------------------------------- hg_aggregate.cpp
 // capacity of a batch's term and chunk lists
 struct FoldCaps {
   size_t terms = 0, chunks = 0;
   void add(size_t bitlen);
 };
-// device-resident requests: their sizes are unknown on the host, every
-// request is bounded by the registry
+// device-resident requests: their sizes are unknown on the host, every request is bounded by the registry
 FoldCaps fold_caps_worst(const hg_ctx* c, size_t n);
+// terms per fold chunk (HG_GT_CHUNK)
+int gt_chunk();
 
 // The parts of a workspace set a batch of n requests needs, sized in one place
 // for a submission and for a lane (every part it may ever use at its largest
@@ -41,16 +66,59 @@ struct AggBatch {
   const FoldCaps* caps = nullptr;
 };
 
-// host-side request validation: the level check of processing.go:350-352
-void level_codes(hg_ctx* c, const hg_request* reqs, size_t n, std::vector<int32_t>& out);
-// the table level an aggregate submission of n requests runs at (counting
-// them towards the volume policy)
-int gt_submission_level(hg_ctx* c, size_t n);
-int gt_acquire(hg_ctx* c, Ws& ws, hipStream_t s, size_t n, const FoldCaps& caps, int& level, GtWork& w,
-               bool may_build = true);
+// The table level of one submission (inside it, on stream s) and its fold work:
+// the policy's level, the tables and fold workspaces it needs (may_build = false:
+// a lane runs at the built level at most), the torus rule, gw's win_bits and torus.
+int submission_level(hg_ctx* c, const AggBatch& b, Ws& ws, hipStream_t s, bool may_build, int& level, GtWork& gw);
+// the GT flows' first launch: level check, signature decode, the fold's counters
 void gt_prologue(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s);
+// the GT fold of the batch into ws.gt_y (codes: in and out)
 void gt_fold(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, int32_t* codes, bool zero_hdr, hipStream_t s);
+// the pairing in its stored form: ws.gt_fe[r] = FE(Miller(G2Base at -sig_r))
 int pair_stored(hg_ctx* c, const AggBatch& b, Ws& ws, SigForm form, hipStream_t s);
+// the stored FE values against ws.gt_y
 void compare_stored(const AggBatch& b, Ws& ws, const GtWork& gw, hipStream_t s);
+// the G2 fold, the GT fold beside it when use_gt, and (verify) the check
 int flow_g2_or_mixed(hg_ctx* c, const AggBatch& b, Ws& ws, bool verify, bool use_gt, bool g2_fold, SigForm form,
                      const GtWork& gw, hipStream_t s);
+// the Combine fold and (verify) the pairing check of a batch on stream s with the workspaces ws (is_lane: a lane's)
+int aggregate_device_locked(hg_ctx* c, const AggBatch& b, bool verify, hipStream_t s, Ws& ws, const SigPolicy& pol,
+                            bool is_lane);
+
+// A host-pointer aggregate batch as its entry point received it (who: its name, for hg_last_error).
+struct HostBatch {
+  const char* who;
+  const hg_request* reqs;
+  size_t n;
+  const uint64_t* words;
+  size_t nwords;
+  const uint8_t* sigs;  // nullable: hg_aggregate_pk has none
+};
+// the host entry points' request check (hg_requests.h, level errors skipped): HG_ERR_ARG with the request named
+// in hg_last_error; lvl (nullable): the level codes; caps (nullable): the fold's exact capacities
+int check_host_requests(hg_ctx* c, const HostBatch& h, int32_t* lvl, FoldCaps* caps);
+// The staging of a host-pointer batch on the context's stream, inside one
+// submission: open() grows the context's staging buffers and uploads requests,
+// words and signatures, put() uploads one more array, close() copies the codes
+// (and the aggregate keys) back and synchronises.
+struct HostStage {
+  hg_ctx* c;
+  Submission sub;
+  uint8_t* d_keys = nullptr;  // the aggregate keys' marshals on the device, when open() was asked for them
+  explicit HostStage(hg_ctx* c_) : c(c_), sub(c_, c_->stream) {}
+  int open(const HostBatch& h, bool want_keys);
+  template <class T>
+  int put(DevBuf<T>& dst, const void* src, size_t count) {
+    HG_CHECK(c, dst.ensure(count));
+    HG_CHECK(c, hipMemcpyAsync(dst.p, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    return HG_OK;
+  }
+  // the staged batch: codes in c->codes_a, keys in d_keys
+  AggBatch batch(const HostBatch& h) const {
+    return AggBatch{c->reqs.p, h.n, c->words.p, h.sigs ? c->bytes_b.p : nullptr, c->codes_a.p, d_keys};
+  }
+  int close(const HostBatch& h, const int32_t* d_codes, int32_t* codes, uint8_t* keys_out);
+};
+// VerifyMultiSignature's requests: the range [0, N) with the multisignature's own bit count
+std::vector<hg_request> multisig_requests(const hg_ctx* c, const uint32_t* bitlens, const uint32_t* word_offsets,
+                                          size_t n);

@@ -1,7 +1,8 @@
 // hg_api.cpp — host side of the C ABI declared in include/handel_gpu.h: the
 // context's lifetime, the message, the registry and the single-check calls.
-// Aggregate verification, its GT tables and the service lanes are in
-// hg_aggregate.cpp, packet intake and the stores in hg_intake.cpp, the batches
+// Aggregate verification is in hg_aggregate.cpp, its GT tables in
+// hg_gttables.cpp, the service lanes in hg_lanes.cpp, its random-linear-
+// combination form in hg_rlc.cpp, packet intake and the stores in hg_intake.cpp, the batches
 // whose checks each carry their own message in hg_msgs.cpp; the state they
 // share is hg_ctx.h.
 //

@@ -1,10 +1,12 @@
 // hg_ctx.h — the state behind the opaque handles of include/handel_gpu.h
 // (hg_ctx, hg_lane, hg_stores) and what every host file of the C ABI shares:
 // the submission chain, phase timing, error reporting. Internal: hg_api.cpp
-// (context, message, registry, single checks), hg_aggregate.cpp (GT tables,
-// aggregate verification, lanes), hg_intake.cpp (packets, stores) and
-// hg_msgs.cpp (checks on their own messages) include it. Every device resource below is held by an owner of hg_dev.h, so
-// deleting a context, a lane or a store set frees what it holds.
+// (context, message, registry, single checks), hg_gttables.cpp (GT tables),
+// hg_aggregate.cpp (aggregate verification), hg_lanes.cpp (service lanes),
+// hg_rlc.cpp (its random-linear-combination form), hg_intake.cpp (packets,
+// stores) and hg_msgs.cpp (checks on their own messages) include it. Every
+// device resource below is held by an owner of hg_dev.h, so deleting a
+// context, a lane or a store set frees what it holds.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -378,6 +380,6 @@ static inline hipError_t ensure_side(Ws& ws) {
 
 // hg_api.cpp: hashedMessage of `msg` as the current message (c->mu held)
 int set_message_locked(hg_ctx* c, const uint8_t* msg, size_t len);
-// hg_aggregate.cpp: what HG_GT_LEVEL / HG_AGG_PATH and HG_GT_OVERLAP give new contexts
+// what HG_GT_LEVEL / HG_AGG_PATH (hg_gttables.cpp) and HG_GT_OVERLAP (hg_aggregate.cpp) give new contexts
 int gt_forced_level();
 bool gt_overlap();

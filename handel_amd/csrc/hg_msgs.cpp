@@ -10,7 +10,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "hg_ctx.h"
+#include "hg_aggregate.h"
 #include "hg_sha256.h"
 
 // the G1 base table, built by the context's first multi-message submission
@@ -162,53 +162,31 @@ static int aggregate_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t
 }
 
 // the host variants: every argument check before anything is launched, then
-// the batch staged on the context's stream. multisig: the requests are
-// VerifyMultiSignature's ([0, N), crypto.go:125-136), whose size check
-// (crypto.go:121-124) has its own code.
-static int aggregate_msgs_host_locked(hg_ctx* c, const char* who, const uint8_t* pool, size_t pool_len,
-                                      const uint32_t* off, const uint32_t* len, const hg_request* reqs, size_t n,
-                                      const uint64_t* words, size_t nwords, const uint8_t* sigs, int32_t* codes,
-                                      uint8_t* agg_out, bool multisig) {
-  int rc = check_ranges(c, who, pool_len, off, len, n);
+// the batch staged on the context's stream (HostStage, hg_aggregate.h) with
+// its messages. multisig: the requests are VerifyMultiSignature's
+// (multisig_requests), whose size check (crypto.go:121-124) has its own code:
+// the level error alone is renamed here.
+static int aggregate_msgs_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* off,
+                                      const uint32_t* len, const HostBatch& h, int32_t* codes, uint8_t* agg_out,
+                                      bool multisig) {
+  const size_t n = h.n;
+  int rc = check_ranges(c, h.who, pool_len, off, len, n);
   if (rc) return rc;
   if (c->nreg == 0) {
-    c->err = std::string(who) + ": needs a registry";
+    c->err = std::string(h.who) + ": needs a registry";
     return HG_ERR_ARG;
   }
-  for (size_t i = 0; i < n; i++) {
-    const hg_request& r = reqs[i];
-    const bool level_ok = r.bitlen == r.level_size && (size_t)r.offset + r.bitlen <= c->nreg;
-    if (!level_ok || (size_t)r.word_offset + ((size_t)r.bitlen + 63) / 64 <= nwords) continue;
-    char buf[160];
-    snprintf(buf, sizeof buf, "%s: request %zu (word offset %u, %u bits) leaves the %zu bitset words", who, i,
-             r.word_offset, r.bitlen, nwords);
-    c->err = buf;
-    return HG_ERR_ARG;
-  }
-  HG_CHECK(c, hipSetDevice(c->device));
-  HG_CHECK(c, c->reqs.ensure(n));
-  HG_CHECK(c, c->words.ensure(nwords ? nwords : 1));
-  HG_CHECK(c, c->codes_a.ensure(n));
-  HG_CHECK(c, c->bytes_b.ensure(n * 64));
-  uint8_t* d_agg = nullptr;
-  if (agg_out) {
-    HG_CHECK(c, c->bytes_a.ensure(n * 128));
-    d_agg = c->bytes_a.p;
-  }
-  Submission sub(c, c->stream);
-  HG_CHECK(c, sub.start());
-  rc = stage_messages(c, pool, pool_len, off, len, n);
+  rc = check_host_requests(c, h, nullptr, nullptr);
   if (rc) return rc;
-  HG_CHECK(c, hipMemcpyAsync(c->reqs.p, reqs, n * sizeof(hg_request), hipMemcpyHostToDevice, c->stream));
-  if (nwords) HG_CHECK(c, hipMemcpyAsync(c->words.p, words, nwords * 8, hipMemcpyHostToDevice, c->stream));
-  HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, c->stream));
-  rc = aggregate_msgs_device_locked(c, c->msgs.pool.p, pool_len, c->msgs.off.p, c->msgs.len.p, c->reqs.p, n,
-                                    c->words.p, c->bytes_b.p, c->codes_a.p, d_agg, c->stream);
+  HostStage st(c);
+  rc = st.open(h, agg_out != nullptr);
+  if (rc == HG_OK) rc = stage_messages(c, pool, pool_len, off, len, n);
   if (rc) return rc;
-  if (agg_out) HG_CHECK(c, hipMemcpyAsync(agg_out, d_agg, n * 128, hipMemcpyDeviceToHost, c->stream));
-  HG_CHECK(c, hipMemcpyAsync(codes, c->codes_a.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HG_CHECK(c, sub.finish());
-  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  const AggBatch b = st.batch(h);
+  rc = aggregate_msgs_device_locked(c, c->msgs.pool.p, pool_len, c->msgs.off.p, c->msgs.len.p, b.reqs, n, b.words,
+                                    b.sigs, b.codes, b.agg, c->stream);
+  if (rc == HG_OK) rc = st.close(h, b.codes, codes, agg_out);
+  if (rc) return rc;
   if (multisig)
     for (size_t i = 0; i < n; i++)
       if (codes[i] == HG_ERR_LEVEL) codes[i] = HG_ERR_MULTI_SIZES;
@@ -240,8 +218,9 @@ int hg_verify_aggregate_msgs(hg_ctx* c, const uint8_t* pool, size_t pool_len, co
     return HG_ERR_ARG;
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  return aggregate_msgs_host_locked(c, "hg_verify_aggregate_msgs", pool, pool_len, msg_off, msg_len, reqs, n, words,
-                                    nwords, sigs, codes, agg_pk_out, false);
+  return aggregate_msgs_host_locked(c, pool, pool_len, msg_off, msg_len,
+                                    HostBatch{"hg_verify_aggregate_msgs", reqs, n, words, nwords, sigs}, codes,
+                                    agg_pk_out, false);
 }
 
 int hg_verify_multisig_msgs(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
@@ -254,10 +233,10 @@ int hg_verify_multisig_msgs(hg_ctx* c, const uint8_t* pool, size_t pool_len, con
   std::lock_guard<std::mutex> g(c->mu);
   // crypto.go:121-124: the bitset must span the registry (bitlen != N is the
   // level error of the request [0, N), renamed); the rest is verifySignature
-  std::vector<hg_request> reqs(n);
-  for (size_t i = 0; i < n; i++) reqs[i] = hg_request{0u, bitlens[i], (uint32_t)c->nreg, word_offsets[i]};
-  return aggregate_msgs_host_locked(c, "hg_verify_multisig_msgs", pool, pool_len, msg_off, msg_len, reqs.data(), n,
-                                    words, nwords, sigs, codes, nullptr, true);
+  const std::vector<hg_request> reqs = multisig_requests(c, bitlens, word_offsets, n);
+  return aggregate_msgs_host_locked(c, pool, pool_len, msg_off, msg_len,
+                                    HostBatch{"hg_verify_multisig_msgs", reqs.data(), n, words, nwords, sigs}, codes,
+                                    nullptr, true);
 }
 
 int hg_verify_batch_msgs_device(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,

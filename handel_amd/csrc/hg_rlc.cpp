@@ -77,16 +77,10 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
   Ws& ws = c->ws;
   Submission sub(c, s);
   HG_CHECK(c, sub.start());
-  int level = gt_submission_level(c, n);
+  int level = 0;
   GtWork gw{};
-  if (level > 0) {
-    int rc = gt_acquire(c, ws, s, n, b.caps ? *b.caps : fold_caps_worst(c, n), level, gw);
-    if (rc) return rc;
-  }
-  // a set in torus form has one fold table, the 16-key windows
-  if (level > 0 && c->cur.gt_level == 2 && c->cur.torus) level = 2;
-  gw.win_bits = level == 2 ? 16 : 8;
-  gw.torus = level == 2 && c->cur.torus;
+  int rc = submission_level(c, b, ws, s, true, level, gw);
+  if (rc) return rc;
   const SigForm form = sig_form(sig_env(), c->pol, n);
   if (level == 0) {
     // no GT flow: the exact path's fold in G2 and two-pairing check
@@ -96,7 +90,7 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
     }
     HG_CHECK(c, ws_ensure(ws, n, kWsG2Fold | kWsVerify | (b.lvl ? 0 : kWsLevel), {}, sig_form_ws_bytes(form, (int)n)));
     PhaseTimer all(c, HG_PHASE_SUBMIT, s);
-    int rc = flow_g2_or_mixed(c, b, ws, true, false, true, form, gw, s);
+    rc = flow_g2_or_mixed(c, b, ws, true, false, true, form, gw, s);
     if (rc) return rc;
     all.stop();
     rc = check_launch(c);
@@ -132,7 +126,7 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
   if (beside) HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
   rlc_g1_sum(ws, b.codes, n, call.group, ng, s);
   const AggBatch gb{nullptr, ng, nullptr, ws.rlc_gsigs.p, ws.rlc_gcodes.p};
-  int rc = pair_stored(c, gb, ws, gform, s);
+  rc = pair_stored(c, gb, ws, gform, s);
   if (rc) return rc;
   if (gw.torus) launch_tor_compare(ws.gt_fe.p, ws.rlc_z.p, (int)ng, ws.rlc_gcodes.p, nullptr, s);
   else launch_gt_compare(ws.gt_fe.p, ws.rlc_z.p, (int)ng, ws.rlc_gcodes.p, s);
@@ -165,47 +159,28 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
 }
 
 // host pointers in, through the context's staging buffers (as hg_verify_aggregate)
-int rlc_host_locked(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
-                    const uint8_t* sigs, const uint64_t* coeffs, const RlcCall& call0, int32_t* codes,
+int rlc_host_locked(hg_ctx* c, const HostBatch& h, const uint64_t* coeffs, const RlcCall& call0, int32_t* codes,
                     int32_t* group_codes, uint32_t* group_live) {
-  HG_CHECK(c, hipSetDevice(c->device));
-  std::vector<int32_t> lvl;
-  level_codes(c, reqs, n, lvl);
   FoldCaps caps;  // exact bounds: the host knows every request's size
-  for (size_t i = 0; i < n; i++) {
-    if (lvl[i] != HG_OK) continue;
-    if ((size_t)reqs[i].word_offset + (reqs[i].bitlen + 63) / 64 > nwords) {
-      c->err = "request words out of range";
-      return HG_ERR_ARG;
-    }
-    caps.add(reqs[i].bitlen);
-  }
-  HG_CHECK(c, c->reqs.ensure(n));
-  HG_CHECK(c, c->words.ensure(nwords ? nwords : 1));
-  HG_CHECK(c, c->codes_a.ensure(n));
-  HG_CHECK(c, c->bytes_b.ensure(n * 64));
-  if (coeffs) HG_CHECK(c, c->bytes_a.ensure(n * 8));
-  Submission sub(c, c->stream);
-  HG_CHECK(c, sub.start());
-  HG_CHECK(c, hipMemcpyAsync(c->reqs.p, reqs, n * sizeof(hg_request), hipMemcpyHostToDevice, c->stream));
-  if (nwords) HG_CHECK(c, hipMemcpyAsync(c->words.p, words, nwords * 8, hipMemcpyHostToDevice, c->stream));
-  HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, c->stream));
-  if (coeffs) HG_CHECK(c, hipMemcpyAsync(c->bytes_a.p, coeffs, n * 8, hipMemcpyHostToDevice, c->stream));
+  int rc = check_host_requests(c, h, nullptr, &caps);
+  if (rc) return rc;
+  HostStage st(c);
+  rc = st.open(h, false);
+  if (rc == HG_OK && coeffs) rc = st.put(c->bytes_a, coeffs, h.n * 8);
+  if (rc) return rc;
   RlcCall call = call0;
   call.d_coeffs = coeffs ? reinterpret_cast<const uint64_t*>(c->bytes_a.p) : nullptr;
-  const AggBatch b{c->reqs.p, n, c->words.p, c->bytes_b.p, c->codes_a.p, nullptr, nullptr, nullptr, &caps};
+  AggBatch b = st.batch(h);
+  b.caps = &caps;
   bool ran = false;
-  int rc = rlc_device_locked(c, b, call, &ran, c->stream);
+  rc = rlc_device_locked(c, b, call, &ran, c->stream);
   if (rc) return rc;
-  HG_CHECK(c, hipMemcpyAsync(codes, c->codes_a.p, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (group_codes && ran) {
-    const size_t ng = (n + call.group - 1) / call.group;
+    const size_t ng = (h.n + call.group - 1) / call.group;
     HG_CHECK(c, hipMemcpyAsync(group_codes, c->ws.rlc_gcodes.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
     HG_CHECK(c, hipMemcpyAsync(group_live, c->ws.rlc_glive.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
   }
-  HG_CHECK(c, sub.finish());
-  HG_CHECK(c, hipStreamSynchronize(c->stream));
-  return HG_OK;
+  return st.close(h, b.codes, codes, nullptr);
 }
 
 bool rlc_group_ok(uint32_t group) { return group >= 1 && group <= kRlcMaxGroup; }
@@ -221,8 +196,8 @@ int hg_verify_aggregate_rlc(hg_ctx* c, const hg_request* reqs, size_t n, const u
   std::lock_guard<std::mutex> g(c->mu);
   c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
   if (n == 0) return HG_OK;
-  return rlc_host_locked(c, reqs, n, words, nwords, sigs, nullptr, RlcCall{seed, nullptr, group, true}, codes, nullptr,
-                         nullptr);
+  return rlc_host_locked(c, HostBatch{"hg_verify_aggregate_rlc", reqs, n, words, nwords, sigs}, nullptr,
+                         RlcCall{seed, nullptr, group, true}, codes, nullptr, nullptr);
 }
 
 int hg_verify_aggregate_rlc_device(hg_ctx* c, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
@@ -291,8 +266,8 @@ int hg_debug_rlc_groups(hg_ctx* c, const hg_request* reqs, size_t n, const uint6
     return HG_ERR_ARG;
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  return rlc_host_locked(c, reqs, n, words, nwords, sigs, coeffs, RlcCall{nullptr, nullptr, group, false}, codes,
-                         group_codes, group_live);
+  return rlc_host_locked(c, HostBatch{"hg_debug_rlc_groups", reqs, n, words, nwords, sigs}, coeffs,
+                         RlcCall{nullptr, nullptr, group, false}, codes, group_codes, group_live);
 }
 
 }  // extern "C"
