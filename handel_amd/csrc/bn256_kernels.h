@@ -32,6 +32,27 @@ struct LineCoef {
   Fp2 bx, cy;
 };
 static constexpr int kNumLines = 65 + 18 + 2;  // doublings + NAF additions + 2 Frobenius lines
+// Two lines that follow each other with nothing between (the doubling's and
+// the addition's of a nonzero NAF digit, and the two Frobenius lines), as ONE
+// factor: with la = Ca + Ba w + w^3, lb alike (B = bx Px, C = cy Py),
+//   la lb = (Ca Cb + xi) + (Ca Bb + Ba Cb) w + Ba Bb w^2 + (Ca + Cb) w^3 + (Ba + Bb) w^4,
+// divided by K3 = cy_a + cy_b, the constant part of its w^3 coefficient K3 Py
+// (an Fp2 factor, removed by the final exponentiation like LineCoef's a):
+//   L = L0 + L1 w + L2 w^2 + Py w^3 + L4 w^4,
+//   L0 = k0 Py^2 + xi, L1 = k1 Px Py, L2 = k2 Px^2, L4 = k4 Px
+// and the constants below (each already divided by K3). K3 != 0 for every pair
+// (tests/test_line_pairs.py); k_g2_lines leaves a pair with K3 = 0 all zero,
+// xi included, which hg_create refuses.
+struct PairCoef {
+  Fp2 k0, xi, k1, k2, k4;  // cy_a cy_b, xi, cy_a bx_b + bx_a cy_b, bx_a bx_b, bx_a + bx_b; all / K3
+};
+static constexpr int kNumPairs = 18 + 1;  // in loop order
+// the line table in HBM: kNumLines LineCoef, then the pair records
+static constexpr int kLineTabEntries =
+    kNumLines + (int)((kNumPairs * sizeof(PairCoef) + sizeof(LineCoef) - 1) / sizeof(LineCoef));
+__host__ __device__ inline const PairCoef* line_pairs(const LineCoef* tab) {
+  return reinterpret_cast<const PairCoef*>(tab + kNumLines);
+}
 
 using AggRequest = hg_request;
 

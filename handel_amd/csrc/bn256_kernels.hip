@@ -269,7 +269,9 @@ __global__ __launch_bounds__(64) void k_hash_point(const uint32_t* k_words, Poin
 // exponentiation. No G2Base line has a = 0 (tests/test_oracle.py).
 // Thread 0 walks the Miller loop and leaves x/crypto's lines in LDS; then one
 // thread per line divides by a (85 Fp2 inversions side by side instead of one
-// after another: the setup kernel 5.0 -> ~1.3 ms).
+// after another: the setup kernel 5.0 -> ~1.3 ms); then one thread per pair of
+// consecutive lines builds its PairCoef behind the table (bn256_kernels.h).
+// tab: kLineTabEntries entries.
 struct RawLine {
   Fp2 a, bx, cy;
 };
@@ -316,8 +318,45 @@ __global__ __launch_bounds__(128) void k_g2_lines(LineCoef* tab) {
   if (j < kNumLines) {
     Fp2 ai;
     f2_inv(ai, raw[j].a);
-    f2_mul(tab[j].bx, raw[j].bx, ai);
-    f2_mul(tab[j].cy, raw[j].cy, ai);
+    f2_mul(raw[j].bx, raw[j].bx, ai);
+    f2_mul(raw[j].cy, raw[j].cy, ai);
+    tab[j].bx = raw[j].bx;
+    tab[j].cy = raw[j].cy;
+  }
+  __syncthreads();
+  // the pair records (PairCoef): thread j < kNumPairs takes the j-th pair of
+  // consecutive lines, from the normalised coefficients left in raw
+  if (j < kNumPairs) {
+    const int8_t naf[kNafLen] = HG_NAF;
+    int a = kNumLines - 2, s = 0, seen = 0;  // the last pair: the two Frobenius lines
+    for (int i = kNafLen - 1; i > 0; i--) {
+      if (naf[i - 1] != 0) {
+        if (seen == j) a = s;
+        seen++;
+        s++;
+      }
+      s++;
+    }
+    const RawLine& la = raw[a];
+    const RawLine& lb = raw[a + 1];
+    Fp2 k3, inv3, t, u, xi;
+    f2_add(k3, la.cy, lb.cy);
+    f2_inv(inv3, k3);  // 0 for K3 = 0: the whole record zero, which hg_create refuses
+    PairCoef pc;
+    f2_mul(t, la.cy, lb.cy);
+    f2_mul(pc.k0, t, inv3);
+    f2_one(xi);
+    f2_mul_xi(xi, xi);
+    f2_mul(pc.xi, xi, inv3);
+    f2_mul(t, la.cy, lb.bx);
+    f2_mul(u, la.bx, lb.cy);
+    f2_add(t, t, u);
+    f2_mul(pc.k1, t, inv3);
+    f2_mul(t, la.bx, lb.bx);
+    f2_mul(pc.k2, t, inv3);
+    f2_add(t, la.bx, lb.bx);
+    f2_mul(pc.k4, t, inv3);
+    reinterpret_cast<PairCoef*>(tab + kNumLines)[j] = pc;
   }
 }
 

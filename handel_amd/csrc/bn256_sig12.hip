@@ -21,6 +21,15 @@
 // decodes each signature once, k_sig_lines runs one product per thread (n x
 // 340 threads: the whole GPU, a few microseconds per batch).
 //
+// Two lines that follow each other with nothing between (a nonzero NAF
+// digit's doubling and addition lines, 18 times, and the two Frobenius lines)
+// are multiplied into f as ONE factor of five coefficients (PairCoef,
+// bn256_kernels.h; the generator's LINE2_FIX_12): one round of 9 products per
+// lane and no linear term where two line rounds ran 4 + 4 and a linear term,
+// each with its own pre-pass, REDC and tail. Such a pair's two rows of ev
+// hold L0, L1 and L2, L4 instead of the two lines, so the 13.6 KB per check
+// stay.
+//
 // Team region (layout T, tools/gen_g2_schedule.py): five Fp12 slots and the
 // register file, 92 elements (kSigTTeamElems; 94 before the shared-operand
 // squaring of r06) — the final exponentiation parks two of its seven live
@@ -29,8 +38,13 @@
 // unpadded kernels' 193-212 VGPRs allow it) beside a fold
 // workgroup.
 //
-// Values are identical to k_verify_sig's (the same Montgomery products in the
-// same order, canonical), so the FE values, and every verdict, are too.
+// The Miller value differs from k_verify_sig's by an Fp2 factor (the pairs'
+// normalisation), which the final exponentiation removes: the FE values are
+// the same field elements, canonical, so their bytes and every verdict are
+// k_verify_sig's (tests/test_gpu_line_pairs.py). One exception, in a value
+// nobody compares: a signature that fails to decode gets the scalars of
+// infinity here (k_sig_scalars), hence FE = 1, where k_verify_sig runs on
+// whatever its coordinates give; its verdict is the decode error either way.
 #include <hip/hip_runtime.h>
 
 #include "bn256_decode.h"
@@ -47,65 +61,134 @@ namespace hg {
 #endif
 static constexpr int kLineBlock = HG_SIG_LINE_BLOCK;
 
-// the signature's evaluation scalars: sc[2c] = x_sig, sc[2c + 1] = -y_sig
-// (both 0 at infinity: e(inf, G2Base) = 1, every line evaluates to w^3, which
-// the final exponentiation maps to 1 — bn256_sigteam.h team_miller_sig). A
-// signature that fails to decode gives meaningless lines: its FE value is
-// never compared (its code is the decode error, k_agg_prologue).
+// How team_miller_sig12 consumes line s of the table: alone, or as the first
+// or second line of a pair (PairCoef `pair`, bn256_kernels.h). From the NAF of
+// 6u + 2, like k_g2_lines' walk.
+enum : uint8_t { kRowSingle = 0, kRowPairFirst = 1, kRowPairSecond = 2 };
+struct SigRowMap {
+  uint8_t kind[kNumLines], pair[kNumLines];
+};
+constexpr SigRowMap sig_row_map() {
+  constexpr int8_t naf[kNafLen] = HG_NAF;
+  SigRowMap m{};
+  int s = 0, p = 0;
+  for (int i = kNafLen - 1; i > 0; i--) {
+    if (naf[i - 1] != 0) {
+      m.kind[s] = kRowPairFirst;
+      m.kind[s + 1] = kRowPairSecond;
+      m.pair[s] = m.pair[s + 1] = (uint8_t)p++;
+      s += 2;
+    } else {
+      m.kind[s++] = kRowSingle;
+    }
+  }
+  m.kind[s] = kRowPairFirst;  // the two Frobenius lines
+  m.kind[s + 1] = kRowPairSecond;
+  m.pair[s] = m.pair[s + 1] = (uint8_t)p;
+  return m;
+}
+static constexpr SigRowMap kSigRows = sig_row_map();
+__constant__ static const SigRowMap kSigRowsDev = sig_row_map();  // k_sig_lines reads it by blockIdx.y
+static_assert(kSigRows.kind[0] == kRowSingle, "team_miller_sig12 seeds f with line 0, a line of its own");
+static_assert(kSigRows.pair[kNumLines - 1] == kNumPairs - 1, "kNumPairs");
+
+// the signature's evaluation scalars: sc[5c ..] = x, y', y'^2, x y', x^2 with
+// x = x_sig, y' = -y_sig. All 0 at infinity — e(inf, G2Base) = 1: every line
+// then evaluates to w^3 and every pair to the Fp2 constant xi / K3, which the
+// final exponentiation maps to 1 — and for a signature that fails to decode,
+// whose FE value is never compared (its code is the decode error,
+// k_agg_prologue).
+static constexpr int kSigScalars = 5;
 __global__ __launch_bounds__(kLineBlock) void k_sig_scalars(const uint8_t* sig_bytes, int flavor, int n, Fp* sc) {
   const int c = blockIdx.x * kLineBlock + threadIdx.x;
   if (c >= n) return;
   PointG1 sg;
-  (void)decode_g1_one(sig_bytes + (size_t)c * 64, flavor, sg);
-  Fp nsy, z;
+  const int32_t code = decode_g1_one(sig_bytes + (size_t)c * 64, flavor, sg);
+  Fp x, y, nsy, z;
   fp_zero(z);
   fp_neg(nsy, sg.y);
-  const bool use = sg.inf == 0;
-  fp_sel(sc[2 * c], use, sg.x, z);
-  fp_sel(sc[2 * c + 1], use, nsy, z);
+  const bool use = sg.inf == 0 && code == HG_OK;
+  fp_sel(x, use, sg.x, z);
+  fp_sel(y, use, nsy, z);
+  Fp* o = sc + (size_t)kSigScalars * c;
+  o[0] = x;
+  o[1] = y;
+  fp_sqr(o[2], y);
+  fp_mul(o[3], x, y);
+  fp_sqr(o[4], x);
 }
 
-// ev[(s * n + c) * 4 + j] = component j of line s at -sig_c: one Montgomery
-// product per thread (FB = bx * x_sig, FC = cy * -y_sig); grid (4n / 256,
-// lines), consecutive threads on consecutive 40-byte results
+// ev[(s * n + c) * 4 + j]: row s of check c. A line of its own: component j of
+// line s at -sig_c (FB = bx x, FC = cy y'). A pair's two rows: L0, L1 then L2,
+// L4 of PairCoef's L (x, y each). One Montgomery product per thread (L0 adds
+// its constant); grid (4n / 256, lines), consecutive threads on consecutive
+// 40-byte results
 __global__ __launch_bounds__(kLineBlock) void k_sig_lines(const Fp* sc, int n, const LineCoef* tab, Fp* ev) {
   const int t = blockIdx.x * kLineBlock + threadIdx.x;  // 4 c + j
   if (t >= 4 * n) return;
   const int s = blockIdx.y;
+  const int kind = kSigRowsDev.kind[s];
   const int j = t & 3;
   const int c = t >> 2;
-  const Fp a = reinterpret_cast<const Fp*>(&tab[s])[j];
-  const Fp b = sc[2 * c + (j >> 1)];
+  const Fp* v = sc + (size_t)kSigScalars * c;
   Fp o;
-  fp_mul(o, a, b);
+  if (kind == kRowSingle) {
+    fp_mul(o, reinterpret_cast<const Fp*>(&tab[s])[j], v[j >> 1]);
+  } else {
+    const Fp* pc = reinterpret_cast<const Fp*>(&line_pairs(tab)[kSigRowsDev.pair[s]]);  // k0, xi, k1, k2, k4 (x, y each)
+    if (kind == kRowPairFirst) {
+      fp_mul(o, pc[j < 2 ? j : 2 + j], v[j < 2 ? 2 : 3]);  // k0 y'^2, k1 x y'
+      if (j < 2) fp_add(o, o, pc[2 + j]);                  // + xi / K3
+    } else {
+      fp_mul(o, pc[6 + j], v[j < 2 ? 4 : 0]);  // k2 x^2, k4 x
+    }
+  }
   st_fp_g8(ev[(size_t)s * 4 * n + t].l, o);
 }
 
-// The evaluated line reaches the team's registers FB, FC through one VGPR
-// element per lane (lane tl < 4 holds Fp tl), read from HBM one publication
-// ahead so the read's latency overlaps the rounds between.
+// The evaluated rows reach the team's registers through one VGPR element per
+// lane, read from HBM one publication ahead so the read's latency overlaps the
+// rounds between: a line of its own (cnt = 4) from lanes 0..3 into FB, FC; a
+// pair (cnt = 8: rows s, s + 1) from lanes 0..7 into FBX, FCY, FB, FC, the
+// generator's LINE2_REGS (L0, L1, L2, L4).
+static_assert(R_FCY_x == R_FBX_x + 2 && R_FB_x == R_FBX_x + 4 && R_FC_x == R_FBX_x + 6, "LINE2_REGS are consecutive");
 struct EvPipe {
   Fp c;
 };
-HG_DEV void ev_fetch(const Team& T, EvPipe& P, const Fp* ev, int n, int ci, int s) {
-  if (T.tl < 4) ld_fp_g8(P.c, ev[((size_t)s * n + ci) * 4 + T.tl].l);
+HG_DEV void ev_fetch(const Team& T, EvPipe& P, const Fp* ev, int n, int ci, int s, int cnt) {
+  if (T.tl < cnt) ld_fp_g8(P.c, ev[((size_t)(s + (T.tl >> 2)) * n + ci) * 4 + (T.tl & 3)].l);
 }
-// the held line into FB, FC, then line `next` into flight
-HG_DEV void ev_publish(const Team& T, uint32_t* F, EvPipe& P, const Fp* ev, int n, int ci, int next) {
-  if (T.tl < 4) st_fp_a8(F + (R_FB_x + T.tl) * 10, P.c.l);
+// the held rows into the registers, then the cnt_next rows from `next` on into
+// flight (cnt_next = 0: none left)
+HG_DEV void ev_publish(const Team& T, uint32_t* F, EvPipe& P, const Fp* ev, int n, int ci, int cnt, int next,
+                       int cnt_next) {
+  if (T.tl < cnt) st_fp_a8(F + ((cnt == 8 ? R_FBX_x : R_FB_x) + T.tl) * 10, P.c.l);
   team_sync();
-  if (next < kNumLines) ev_fetch(T, P, ev, n, ci, next);
+  if (cnt_next > 0) ev_fetch(T, P, ev, n, ci, next, cnt_next);
 }
 
 using ISqr12T = XInst<XP_SQR12_12_T, S_F, S_F>;
 using ILineT = XInst<XP_LINE_FIX_12_T, S_F, S_F>;
+using ILine2T = XInst<XP_LINE2_FIX_12_T, S_F, S_F>;
 
 // Miller(G2Base at -sig) over the NAF of 6u + 2 (bn256_sigteam.h
-// team_miller_sig's loop; the lines arrive evaluated): f^2, then f * line
-// per digit (two lines on a nonzero digit), then the two Frobenius lines
-HG_DEV void team_miller_sig12(const Team& T, uint32_t* F, const Fp* ev, int n, int ci, XStream& S, XHint after) {
+// team_miller_sig's loop; the rows arrive evaluated), up to an Fp2 factor that
+// the final exponentiation removes: f starts as the first line (not as 1,
+// squared and multiplied by it); then per digit f^2 and f * line, on a
+// nonzero digit f * (the doubling's line * the addition's) in ONE round
+// (LINE2_FIX_12); then the two Frobenius lines, one round as well.
+HG_DEV void team_miller_sig12(const Team& T, uint32_t* F, const Fp* ev, const Fp* sc, int n, int ci, XStream& S,
+                              XHint after) {
   const int8_t naf[kNafLen] = HG_NAF;
-  t12_set_one(T, S_F);
+  {
+    // f = FC + FB w + w^3 of row 0: element e < 4 is the row's component e ^ 2
+    Fp v, one;
+    fp_zero(v);
+    fp_one(one);
+    if (T.tl < 4) ld_fp_g8(v, ev[(size_t)ci * 4 + (T.tl ^ 2)].l);
+    fp_sel(v, T.e == 7, one, v);  // element 7 = c3.y
+    if (T.active) st_fp_a8(slot(T, S_F) + T.e * 10, v.l);
+  }
   if (T.tl == 0) {
     Fp zero, one;
     fp_zero(zero);
@@ -113,31 +196,31 @@ HG_DEV void team_miller_sig12(const Team& T, uint32_t* F, const Fp* ev, int n, i
     st_fp(F + R_ZERO * 10, zero);
     st_fp(F + R_ONE * 10, one);
   }
-  team_sync();
+  if (T.tl == 1) {  // y', the pairs' w^3 coefficient
+    Fp y;
+    ld_fp_g8(y, sc[(size_t)kSigScalars * ci + 1].l);
+    st_fp_a8(F + R_NSY * 10, y.l);
+  }
   EvPipe P;
   fp_zero(P.c);
-  ev_fetch(T, P, ev, n, ci, 0);
-  int s = 0;
-  for (int i = kNafLen - 1; i > 0; i--) {
+  int s = 1;
+  ev_fetch(T, P, ev, n, ci, s, naf[kNafLen - 3] != 0 ? 8 : 4);
+  for (int i = kNafLen - 2; i > 0; i--) {
     const int d = naf[i - 1];
-    ev_publish(T, F, P, ev, n, ci, s + 1);  // line s, read by the product after f^2
-    ISqr12T::run(T, S, xh<ILineT>());      // f^2 (f = 1 on the first digit)
-    const XHint after_digit = i > 1 ? xh<ISqr12T>() : xh<ILineT>();
-    if (d != 0) {
-      ILineT::run(T, S, xh<ILineT>());
-      ev_publish(T, F, P, ev, n, ci, s + 2);  // line s + 1 (the addition's)
-      ILineT::run(T, S, after_digit);
-      s += 2;
-    } else {
-      ILineT::run(T, S, after_digit);
-      s += 1;
-    }
+    const int cnt = d != 0 ? 8 : 4;
+    const int next = s + (cnt >> 2);
+    // what the following digit reads; after the last one, the Frobenius pair
+    const int cnt_next = i > 1 && naf[i - 2] == 0 ? 4 : 8;
+    ev_publish(T, F, P, ev, n, ci, cnt, next, cnt_next);  // read by the product after f^2
+    ISqr12T::run(T, S, d != 0 ? xh<ILine2T>() : xh<ILineT>());
+    const XHint after_digit = i > 1 ? xh<ISqr12T>() : xh<ILine2T>();
+    if (d != 0) ILine2T::run(T, S, after_digit);
+    else ILineT::run(T, S, after_digit);
+    s = next;
   }
   // the two Frobenius lines
-  ev_publish(T, F, P, ev, n, ci, s + 1);
-  ILineT::run(T, S, xh<ILineT>());
-  ev_publish(T, F, P, ev, n, ci, kNumLines);
-  ILineT::run(T, S, after);
+  ev_publish(T, F, P, ev, n, ci, 8, kNumLines, 0);
+  ILine2T::run(T, S, after);
 }
 
 // What every 12-lane pairing kernel starts with, after its LDS array
@@ -183,14 +266,15 @@ struct Sig12Park {
 // overwrites it) and park[r]. kPad: one pairing wave per SIMD (as
 // k_verify_sig's default); unpadded, two batches' waves share a SIMD.
 template <bool kPad>
-__global__ __launch_bounds__(64, kPad ? 1 : 2) void k_verify_sig12(const Fp* ev, int n, Gt* fe, Gt* park) {
+__global__ __launch_bounds__(64, kPad ? 1 : 2) void k_verify_sig12(const Fp* ev, const Fp* sc, int n, Gt* fe,
+                                                                   Gt* park) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[kSig12LdsWords];
   uint32_t* F;
   int idx, ci;
   bool valid;
   Team T = sig12_team<kPad>(lds, n, F, idx, valid, ci);
   XStream S = x_stream();
-  team_miller_sig12(T, F, ev, n, ci, S, SigFE<SigProgs12>::final_exp_hint_t());
+  team_miller_sig12(T, F, ev, sc, n, ci, S, SigFE<SigProgs12>::final_exp_hint_t());
   SigFE<SigProgs12>::team_final_exp_fc_t(T, S, Sig12Park{fe, park, n});
   team_sync();
   Fp v;
@@ -238,15 +322,15 @@ HG_DEV void sig12_store_terms(const Team& T, bool valid, const NormTerms& o, con
 }
 
 template <bool kPad>
-__global__ __launch_bounds__(64, kPad ? 1 : 2) void k_sig12_miller(const Fp* ev, int n, Gt* fe, SigHand* hand,
-                                                                   Fp* nrm) {
+__global__ __launch_bounds__(64, kPad ? 1 : 2) void k_sig12_miller(const Fp* ev, const Fp* sc, int n, Gt* fe,
+                                                                   SigHand* hand, Fp* nrm) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[kSig12LdsWords];
   uint32_t* F;
   int idx, ci;
   bool valid;
   Team T = sig12_team<kPad>(lds, n, F, idx, valid, ci);
   XStream S = x_stream();
-  team_miller_sig12(T, F, ev, n, ci, S, xh<ISqr12T>());
+  team_miller_sig12(T, F, ev, sc, n, ci, S, xh<ISqr12T>());
   SigFE<SigProgs12>::fe_t_norm(T, S, xh_none());
   NormTerms o;
   Fp nr;
@@ -397,7 +481,7 @@ struct Sig12Layout {
     auto align256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     park = lines ? align256((size_t)n * kNumLines * 4 * sizeof(Fp)) : 0;
     scalars = park + align256((size_t)(n + 1 + 2 * kTeams12) * sizeof(Gt));
-    hand = scalars + (lines ? align256((size_t)n * 2 * sizeof(Fp)) : 0);
+    hand = scalars + (lines ? align256((size_t)n * kSigScalars * sizeof(Fp)) : 0);
     norm = hand + align256((size_t)n * sizeof(SigHand));
     ninv = norm + align256((size_t)n * sizeof(Fp));
     bytes = ninv + (size_t)n * sizeof(Fp);
@@ -411,12 +495,13 @@ size_t fe12_ws_bytes(int n) { return Sig12Layout(n, false).bytes; }
 // of the Miller values already in fe; then the batched inversion and the rest
 // of the final exponentiation, in place.
 static void launch_split_chain(const Fp* ev, int n, Gt* fe, uint8_t* base, const Sig12Layout& L, hipStream_t s) {
+  const Fp* sc = (const Fp*)(base + L.scalars);
   Gt* park = (Gt*)(base + L.park);
   SigHand* hand = (SigHand*)(base + L.hand);
   Fp* nrm = (Fp*)(base + L.norm);
   Fp* ninv = (Fp*)(base + L.ninv);
   const int blocks = (n + kTeams12 - 1) / kTeams12;
-  if (ev) k_sig12_miller<false><<<blocks, 64, 0, s>>>(ev, n, fe, hand, nrm);
+  if (ev) k_sig12_miller<false><<<blocks, 64, 0, s>>>(ev, sc, n, fe, hand, nrm);
   else k_sig12_norm<<<blocks, 64, 0, s>>>(n, fe, hand, nrm);
   k_sig12_ninv<<<(n + kInvBlock - 1) / kInvBlock, kInvBlock, 0, s>>>(nrm, n, ninv);
   k_sig12_fe<false><<<blocks, 64, 0, s>>>(n, fe, park, hand, ninv);
@@ -445,8 +530,8 @@ bool launch_sig12(bool pad, bool split, const uint8_t* sigs, int flavor, int n, 
   const int blocks = (n + kTeams12 - 1) / kTeams12;
   Gt* park = (Gt*)(ws + L.park);
   if (split) launch_split_chain(ev, n, fe, ws, L, s);
-  else if (pad) k_verify_sig12<true><<<blocks, 64, 0, s>>>(ev, n, fe, park);
-  else k_verify_sig12<false><<<blocks, 64, 0, s>>>(ev, n, fe, park);
+  else if (pad) k_verify_sig12<true><<<blocks, 64, 0, s>>>(ev, sc, n, fe, park);
+  else k_verify_sig12<false><<<blocks, 64, 0, s>>>(ev, sc, n, fe, park);
   return true;
 }
 

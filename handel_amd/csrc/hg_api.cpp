@@ -17,6 +17,7 @@
 // nil-aggregate panic > pairing verdict.
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "hg_ctx.h"
 #include "hg_sha256.h"
@@ -183,7 +184,7 @@ int hg_create(int device, int flavor, hg_ctx** out) {
   c->verify_split = sig_env().verify_split;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = c->stream.create(hipStreamNonBlocking);
-  if (e == hipSuccess) e = c->d_lines.alloc(kNumLines);
+  if (e == hipSuccess) e = c->d_lines.alloc(kLineTabEntries);
   if (e == hipSuccess) e = c->cur.d_h.alloc(1);
   if (e == hipSuccess) e = c->d_k.alloc(8);
   if (e != hipSuccess) {
@@ -194,6 +195,21 @@ int hg_create(int device, int flavor, hg_ctx** out) {
   launch_g2_lines(c->d_lines.p, c->stream);
   if (check_launch(c) != HG_OK || hipStreamSynchronize(c->stream) != hipSuccess) {
     fprintf(stderr, "hg_create: %s\n", c->err.c_str());
+    delete c;
+    return HG_ERR_DEVICE;
+  }
+  // a pair of consecutive lines whose w^3 coefficient vanishes has an all-zero
+  // record (k_g2_lines): a fact about the curve's constants that never holds
+  std::vector<PairCoef> pairs(kNumPairs);
+  bool pairs_ok = hipMemcpy(pairs.data(), line_pairs(c->d_lines.p), kNumPairs * sizeof(PairCoef),
+                            hipMemcpyDeviceToHost) == hipSuccess;
+  for (const PairCoef& pc : pairs) {
+    uint32_t any = 0;
+    for (int l = 0; l < 10; l++) any |= pc.xi.x.l[l] | pc.xi.y.l[l];
+    pairs_ok = pairs_ok && any != 0;
+  }
+  if (!pairs_ok) {
+    fprintf(stderr, "hg_create: a G2Base line pair has no w^3 coefficient\n");
     delete c;
     return HG_ERR_DEVICE;
   }

@@ -496,6 +496,44 @@ def prog_line_n(lb, lc):
     return [lanes]
 
 
+def prog_line2_n(l0, l1, l2, l4, y):
+    """dst = A * (l0 + l1 w + l2 w^2 + y w^3 + l4 w^4), y an Fp scalar
+    register: the product of two consecutive normalised G2Base lines (a
+    doubling's and its addition's, or the two Frobenius lines) divided by the
+    constant Fp2 part K3 of its w^3 coefficient K3 y', a factor the final
+    exponentiation removes like prog_line_n's a (bn256_kernels.hip k_g2_lines
+    has the pair constants, bn256_sig12.hip k_sig_lines the coefficients). One
+    round of 9 products per lane, no linear term, instead of prog_line_n's two
+    rounds. (Dividing by y' as well would make the w^3 part a linear term, 8
+    products; the inversion it needs costs the headline more than the product:
+    DESIGN.md 3d.) xi sits on the line coefficient of a wrapped term and, for
+    the w^3 part, on A (twelve pre-pass values), the y components' sign on the
+    A side, -A_i.x (six more): eighteen values, at most two per lane of a
+    12-lane team."""
+    lanes = []
+    for k in range(6):
+        for c in "xy":
+            slots = []
+            for jpos, L in ((0, l0), (1, l1), (2, l2), (4, l4)):
+                i = k - jpos
+                lx, ly = [(comp(L, "x"), 1)], [(comp(L, "y"), 1)]
+                if i < 0:
+                    i += 6
+                    lx, ly = xi_lc(lx, ly)
+                fx, fy = [(comp(f"A{i}", "x"), 1)], [(comp(f"A{i}", "y"), 1)]
+                if c == "x":
+                    slots += [(fx, ly), (fy, lx)]
+                else:
+                    slots += [(fy, ly), (neg(fx), lx)]
+            i = k - 3
+            fx, fy = [(comp(f"A{i % 6}", "x"), 1)], [(comp(f"A{i % 6}", "y"), 1)]
+            if i < 0:
+                fx, fy = xi_lc(fx, fy)   # xi * A_{k+3}
+            slots.append((fx if c == "x" else fy, scal(y)))
+            lanes.append(Lane(comp(f"D{k}", c), slots))
+    return [lanes]
+
+
 def prog_tor_mul():
     """dst = A * (alpha + w) for A = n + d w (n = the even powers of w, d the odd
     ones: Fp6 = Fp2[v]/(v^3 - xi), v = w^2) and alpha in Fp6 in elements 0..5 of
@@ -565,6 +603,11 @@ PROGRAMS["SQR12_12"] = prog_sqr12()
 PROGRAMS["LINE_FIX_12"] = prog_line_n("FB", "FC")
 PROGRAMS["MUL12_12"] = prog_mul12()
 PROGRAMS["CYC_SQR_X_12"] = prog_cyc_sqr_x_shared()  # r06: 24 pre-pass values (two per lane)
+# f times a PAIR of consecutive lines in one round (team_miller_sig12's nonzero
+# digits and its two Frobenius lines): the coefficients L0, L1, L2, L4 in the
+# eight consecutive registers FBX, FCY, FB, FC, and y' in NSY
+LINE2_REGS = ("FBX", "FCY", "FB", "FC")
+PROGRAMS["LINE2_FIX_12"] = prog_line2_n(*LINE2_REGS, "NSY")
 # k_tor_chunks (bn256_gt.hip): a running product times a table entry in torus
 # form, in the GT-fold team layout (context FOLD), 12-lane teams
 PROGRAMS["TORMULF"] = prog_tor_mul()
@@ -962,7 +1005,8 @@ def run_xround(xr, F, A, B, limbs=False):
 X_FETCH_WORDS = 16  # words per lane one table prefetch brings in (>= the widest round)
 # programs whose pre-pass values live on lanes 0..11 only, so that they also
 # run in 12-lane teams (five per wave: k_gt_chunks, make_team12)
-PRE_LANES = {"MUL12F": 12, "SQR12_12": 12, "LINE_FIX_12": 12, "MUL12_12": 12, "CYC_SQR_X_12": 12, "TORMULF": 12}
+PRE_LANES = {"MUL12F": 12, "SQR12_12": 12, "LINE_FIX_12": 12, "MUL12_12": 12, "CYC_SQR_X_12": 12, "TORMULF": 12,
+             "LINE2_FIX_12": 12}
 KARATSUBA_MIN = 4   # jobs of this many products use Karatsuba (when check_xround allows)
 # Per-program thresholds. The default counts instructions: a Karatsuba product
 # saves 25 mads for 10 limb additions, and the job's column combination (~55
@@ -990,6 +1034,7 @@ X_PROGRAMS = {  # name -> (program, scratch context)
     "FEVAL": "ML", "SDBL": "ML", "LFEV": "ML", "MUL12F": "FOLD",
     "SQR12_12": "ML", "LINE_FIX_12": "ML", "MUL12_12": "FE", "CYC_SQR_X_12": "FE",
     "TORMULF": "FOLD",
+    "LINE2_FIX_12": "ML",
 }
 
 
@@ -1188,6 +1233,15 @@ def validate_x(seed=2):
         assert unflat(run_xprogram(X["LINE_FIX"], G, flat(f))) == O._mul_line(f, O.F2_ONE, lb, lc), "xLINE_FIX"
         assert unflat(run_xprogram(X["LINE_FIX_12"], G, flat(f))) == O._mul_line(f, O.F2_ONE, lb, lc), \
             "xLINE_FIX_12"
+        # the pair form: f * (l0 + l1 w + l2 w^2 + y w^3 + l4 w^4), pre-pass values on lanes 0..11
+        l4 = [(rng.randrange(P), rng.randrange(P)) for _ in range(4)]
+        for n, v in zip(LINE2_REGS, l4):
+            put(G, n, v)
+        pair = [l4[0], l4[1], l4[2], (0, G[REG["NSY"]]), l4[3], (0, 0)]
+        assert unflat(run_xprogram(X["LINE2_FIX_12"], G, flat(f))) == O.f12_mul(f, pair), "xLINE2_FIX_12"
+        (xr2,) = X["LINE2_FIX_12"]
+        assert (xr2.nv, xr2.np, xr2.nl) == (2, 9, 0) and xr2.ks1, "LINE2_FIX_12"
+        assert all(d == NONE for L in xr2.lanes[12:] for d, _ in L["pre"]), "LINE2_FIX_12"
     return X
 
 
@@ -1301,6 +1355,17 @@ TOR_INSTANCES = [("TORMULF", ("A", "A", "B"))]
 ALL_INSTANCES = ([(n, b, "") for n, b in INSTANCES] + [(n, b, "S") for n, b in SIG_INSTANCES]
                  + [(n, b, "T") for n, b in SIG_T_INSTANCES] + [(n, b, "V") for n, b in V_INSTANCES]
                  + [(n, b, "") for n, b in TOR_INSTANCES])
+# team_miller_sig12's pair product, bound on layout T. A list of its own:
+# ALL_INSTANCES numbers the instance probe's cases (bn256_xprobe.h), which stay
+# as they are; the tables, the region check and check_instances take both
+# lists (BOUND_INSTANCES), the fold's instance still last.
+PAIR_INSTANCES = [("LINE2_FIX_12", ("F", "F"), "T")]
+# The probe runs them too, behind its numbered cases: instance k of
+# PAIR_INSTANCES is probe instance PROBE_EXTRA_BASE + k (hg_debug_xinst), and
+# entry len(ALL_INSTANCES) + k of PROBE_INSTANCES, kXProbeInfo and instance_rounds.
+PROBE_EXTRA_BASE = 1 << 16
+PROBE_INSTANCES = ALL_INSTANCES + PAIR_INSTANCES
+BOUND_INSTANCES = ALL_INSTANCES[:-len(TOR_INSTANCES)] + PAIR_INSTANCES + ALL_INSTANCES[-len(TOR_INSTANCES):]
 
 
 
@@ -1541,7 +1606,7 @@ def run_bound_limbs(rounds, mem):
 def check_instances(X, seed=3):
     """Every bound instance computes the same as the abstract program."""
     rng = random.Random(seed)
-    for name, binding, layout in ALL_INSTANCES:
+    for name, binding, layout in BOUND_INSTANCES:
         ctx = X_PROGRAMS[name]
         fb = {"S": SIG_F_BASE, "T": SIG_T_F_BASE, "V": V_F_BASE}.get(layout, F_BASE_CTX[ctx])
         rounds = [bind(xr, binding, ctx, layout) for xr in X[name]]
@@ -1573,7 +1638,7 @@ def check_instances(X, seed=3):
 # the final exponentiation); its team region ends after the last element they
 # (and the hand-written helpers: registers up to FC) touch
 SIG_PROGRAMS = ("SDBL", "LFEV", "FEVAL", "LINE_FIX", "MUL12", "CYC_SQR_X", "CYC_SQR",
-                "SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12")
+                "SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12", "LINE2_FIX_12")
 
 
 # REDC fusion (x_round's FU, bn256_xprog.h x_job): the job's last product runs
@@ -1588,7 +1653,7 @@ SIG_PROGRAMS = ("SDBL", "LFEV", "FEVAL", "LINE_FIX", "MUL12", "CYC_SQR_X", "CYC_
 # and every product of theirs is a 75-mad Karatsuba product (measured, with
 # the cyclotomic squaring's third product fused and not:
 # profiles/r07ks_levers_ab.json).
-REDC_FUSE_OFF = ("SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12")
+REDC_FUSE_OFF = ("SQR12_12", "LINE_FIX_12", "MUL12_12", "CYC_SQR_X_12", "LINE2_FIX_12")
 REDC_FUSE = {name: (ctx == "FE" or name in SIG_PROGRAMS) and name not in REDC_FUSE_OFF
              for name, ctx in X_PROGRAMS.items()}
 REDC_FUSE["TORMULF"] = False  # the fold's: several waves per SIMD, as MUL12F
@@ -1612,7 +1677,7 @@ def region_ends(X):
     sig_end = SIG_F_BASE + REG["FC.y"] + 1  # team_miller_sig's registers: ZERO .. FC
     sig_t_end = SIG_T_F_BASE + REG["FC.y"] + 1  # team_miller_sig12's: ZERO, ONE, FB, FC
     fold_end = FOLD_F_BASE + 2               # ZERO, ONE
-    for name, binding, layout in ALL_INSTANCES:
+    for name, binding, layout in BOUND_INSTANCES:
         ctx = X_PROGRAMS[name]
         for xr in X[name]:
             t = touched(bind(xr, binding, ctx, layout)) + 1
@@ -1627,9 +1692,9 @@ def region_ends(X):
 
 def emit_x(X, path):
     sig_end, sig_t_end, fold_end = region_ends(X)
-    sig_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "S"}, key=list(X_PROGRAMS).index)
-    sig_t_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "T"}, key=list(X_PROGRAMS).index)
-    v_names = sorted({n for n, _, lay in ALL_INSTANCES if lay == "V"}, key=list(X_PROGRAMS).index)
+    sig_names = sorted({n for n, _, lay in BOUND_INSTANCES if lay == "S"}, key=list(X_PROGRAMS).index)
+    sig_t_names = sorted({n for n, _, lay in BOUND_INSTANCES if lay == "T"}, key=list(X_PROGRAMS).index)
+    v_names = sorted({n for n, _, lay in BOUND_INSTANCES if lay == "V"}, key=list(X_PROGRAMS).index)
     v_end = V_F_BASE + NREGS
     lines = ["// Generated by tools/gen_g2_schedule.py — do not edit.",
              "// Two-phase team programs executed by bn256_xprog.h (encoding: see there),",
@@ -1651,7 +1716,7 @@ def emit_x(X, path):
              f"static constexpr int kVTeamElems = {v_end + v_end % 2};  // k_verify_ml's team region",
              "template <int PROG, int D = -1, int A = -1, int B = -1> struct XInst;"]
     words = []
-    for name, binding, layout in ALL_INSTANCES:
+    for name, binding, layout in BOUND_INSTANCES:
         ctx = X_PROGRAMS[name]
         rounds = []
         for xr in X[name]:
@@ -1723,8 +1788,9 @@ def probe_reg_base(name, layout):
 
 
 def instance_rounds(X, i):
-    """The bound rounds of instance i of ALL_INSTANCES (run_bound / run_bound_limbs run them)."""
-    name, binding, layout = ALL_INSTANCES[i]
+    """The bound rounds of entry i of PROBE_INSTANCES: instance i of ALL_INSTANCES,
+    then PAIR_INSTANCES (run_bound / run_bound_limbs run them)."""
+    name, binding, layout = PROBE_INSTANCES[i]
     return [bind(xr, binding, X_PROGRAMS[name], layout) for xr in X[name]]
 
 
@@ -1733,7 +1799,7 @@ def probe_groups():
     of PROBE_GROUP_MAX, one probe kernel per chunk."""
     groups = []
     for lay in PROBE_LAYOUTS:
-        idx = [i for i, (n, _, l) in enumerate(ALL_INSTANCES) if probe_layout(n, l) == lay]
+        idx = [i for i, (n, _, l) in enumerate(PROBE_INSTANCES) if probe_layout(n, l) == lay]
         groups += [(lay, idx[k:k + PROBE_GROUP_MAX]) for k in range(0, len(idx), PROBE_GROUP_MAX)]
     return groups
 
@@ -1742,10 +1808,11 @@ def emit_xprobe(X, path):
     elems = probe_region_elems(X)
     groups = probe_groups()
     group_of = {i: g for g, (_, idx) in enumerate(groups) for i in idx}
-    assert sorted(group_of) == list(range(len(ALL_INSTANCES)))
+    assert sorted(group_of) == list(range(len(PROBE_INSTANCES)))
     lines = ["// Generated by tools/gen_g2_schedule.py — do not edit.",
              "// The instance probe's dispatch (bn256_xprobe_kernel.h, hg_debug_xinst): instance i",
-             "// is entry i of the generator's ALL_INSTANCES. kXProbeInfo gives its team",
+             "// is entry i of the generator's ALL_INSTANCES, instance kXProbeExtraBase + k entry",
+             "// kXProbeInstances + k of the tables here (PAIR_INSTANCES). kXProbeInfo gives its team",
              "// region (a probe layout and its element count) and the probe kernel (group)",
              "// that holds it; XProbeGroup<G>::run is that kernel's switch over its instances,",
              "// each case the call XInst<...>::run of the instance's call sites.",
@@ -1754,9 +1821,10 @@ def emit_xprobe(X, path):
              + " };  // full region, layouts S, T, V, FOLD context",
              "struct XProbeInfo { unsigned char layout, group; unsigned short elems; };",
              f"static constexpr int kXProbeInstances = {len(ALL_INSTANCES)};",
+             f"static constexpr int kXProbeExtra = {len(PAIR_INSTANCES)}, kXProbeExtraBase = {PROBE_EXTRA_BASE};",
              f"static constexpr int kXProbeGroups = {len(groups)};",
-             f"static constexpr XProbeInfo kXProbeInfo[kXProbeInstances] = {{"]
-    for i, (name, binding, layout) in enumerate(ALL_INSTANCES):
+             f"static constexpr XProbeInfo kXProbeInfo[kXProbeInstances + kXProbeExtra] = {{"]
+    for i, (name, binding, layout) in enumerate(PROBE_INSTANCES):
         lay = probe_layout(name, layout)
         lines.append(f"  {{XPL_{lay}, {group_of[i]}, {elems[lay]}}},  // {i}: {name}"
                      f"{'_' + layout if layout else ''}<{', '.join(binding)}>")
@@ -1770,7 +1838,7 @@ def emit_xprobe(X, path):
         lines.append(f"template <> struct XProbeGroup<{g}> {{ HG_DEV static void run(int inst, const Team& T, XStream& S) {{")
         lines.append("  switch (inst) {  // kernel-uniform")
         for i in idx:
-            name, binding, layout = ALL_INSTANCES[i]
+            name, binding, layout = PROBE_INSTANCES[i]
             targs = f"XP_{name}{'_' + layout if layout else ''}" + "".join(f", S_{b}" for b in binding)
             lines.append(f"    case {i}: XInst<{targs}>::run(T, S, xh_none()); break;")
         lines.append("    default: break;")
@@ -1803,7 +1871,7 @@ if __name__ == "__main__":
     check_instances(Xp)
     nwords = emit_x(Xp, os.path.join(csrc, "bn256_xtab.h"))
     ngroups = emit_xprobe(Xp, os.path.join(csrc, "bn256_xprobe.h"))
-    print(len(ALL_INSTANCES), "instances,", nwords * 4, "table bytes,", ngroups, "probe kernels")
+    print(len(BOUND_INSTANCES), "instances,", nwords * 4, "table bytes,", ngroups, "probe kernels")
     for name, rounds in Xp.items():
         print(name, [(r.nv, r.nt, r.np, r.nl, r.words()) for r in rounds])
     print("validated and wrote bn256_regs.h, bn256_xtab.h, bn256_xprobe.h")
