@@ -557,6 +557,82 @@ func (e *Engine) VerifyMultiSignaturesMsgs(msgs [][]byte, bitLens []int, words [
 	return codes, nil
 }
 
+// VerifyMultiSignaturesMsgsRLC is VerifyMultiSignaturesMsgs with the final
+// exponentiations of `group` multisignatures at a time replaced by one, under
+// random coefficients from crypto/rand (hg_verify_multisig_msgs_rlc): the same
+// code per multisignature (crypto.go:120-137, processing.go:342-368), except
+// that an invalid signature is accepted with probability at most 2^-64. Groups
+// that fail are verified one by one. For callers whose multisignatures are
+// almost all valid (a node catching up, a monitor, a bridge); RLCStats reports
+// on the call. group <= 0 selects DefaultRLCGroup; the largest group is 4096.
+func (e *Engine) VerifyMultiSignaturesMsgsRLC(msgs [][]byte, bitLens []int, words [][]uint64, sigs []byte,
+	group int) ([]int32, error) {
+	n := len(msgs)
+	if len(bitLens) != n || len(words) != n || len(sigs) != 64*n {
+		return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyMultiSignaturesMsgsRLC: sizes"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	if group <= 0 {
+		group = DefaultRLCGroup
+	}
+	seed, err := rlcSeed()
+	if err != nil {
+		return nil, err
+	}
+	pool, off, ln, err := packMessages("VerifyMultiSignaturesMsgsRLC", msgs)
+	if err != nil {
+		return nil, err
+	}
+	size := int(C.hg_registry_size(e.ctx))
+	lens := make([]uint32, n)
+	woff := make([]uint32, n)
+	var all []uint64
+	for i := range lens {
+		if bitLens[i] < 0 || bitLens[i] > math.MaxUint32 || len(words[i]) < (bitLens[i]+63)/64 {
+			return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: fmt.Sprintf("multisignature %d: malformed bitset", i)}
+		}
+		lens[i], woff[i] = uint32(bitLens[i]), uint32(len(all))
+		if bitLens[i] == size { // any other length fails the size check; its words are never read
+			all = append(all, words[i][:(bitLens[i]+63)/64]...)
+		}
+	}
+	codes := failedCodes(n)
+	rc := C.hg_verify_multisig_msgs_rlc(e.ctx, bytePtr(pool), C.size_t(len(pool)), (*C.uint32_t)(unsafe.Pointer(&off[0])),
+		(*C.uint32_t)(unsafe.Pointer(&ln[0])), (*C.uint32_t)(unsafe.Pointer(&lens[0])),
+		(*C.uint32_t)(unsafe.Pointer(&woff[0])), C.size_t(n), wordPtr(all), C.size_t(len(all)), bytePtr(sigs),
+		(*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint32_t(group), codePtr(codes))
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
+	}
+	return codes, nil
+}
+
+// VerifyAggregateMsgsRLCDevice is the same form for device-resident aggregate
+// requests that each carry their own message: the pool, offsets, lengths,
+// requests, bitset words, signatures and codes are device pointers
+// (hg_verify_aggregate_msgs_rlc_device). It synchronises `stream` once: the
+// number of requests in failed groups comes back to the host to size their
+// exact recheck.
+func (e *Engine) VerifyAggregateMsgsRLCDevice(dPool unsafe.Pointer, poolLen int, dMsgOff, dMsgLen, dReqs unsafe.Pointer,
+	n int, dWords, dSigs unsafe.Pointer, group int, dCodes, stream unsafe.Pointer) error {
+	if group <= 0 {
+		group = DefaultRLCGroup
+	}
+	seed, err := rlcSeed()
+	if err != nil {
+		return err
+	}
+	rc := C.hg_verify_aggregate_msgs_rlc_device(e.ctx, (*C.uint8_t)(dPool), C.size_t(poolLen), (*C.uint32_t)(dMsgOff),
+		(*C.uint32_t)(dMsgLen), (*C.hg_request)(dReqs), C.size_t(n), (*C.uint64_t)(dWords), (*C.uint8_t)(dSigs),
+		(*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint32_t(group), (*C.int32_t)(dCodes), stream)
+	if rc != C.HG_OK {
+		return e.fail(rc)
+	}
+	return nil
+}
+
 // CombineG1 is SigBLS.Combine batched: out[i] = a[i] + b[i] (64-byte marshals).
 func (e *Engine) CombineG1(a, b []byte) ([]byte, []int32, error) {
 	n := len(a) / 64

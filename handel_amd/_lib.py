@@ -112,6 +112,11 @@ SIGNATURES = {
     "hg_debug_rlc_coeffs": (_I, [_P, ctypes.c_uint64, _SZ, _P]),
     "hg_debug_rlc_g1": (_I, [_P, _P, _SZ, _P, ctypes.c_uint32, _P]),
     "hg_debug_rlc_groups": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "hg_verify_aggregate_msgs_rlc": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P]),
+    "hg_verify_aggregate_msgs_rlc_device": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, ctypes.c_uint32, _P, _P]),
+    "hg_verify_multisig_msgs_rlc": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P]),
+    "hg_debug_msgs_rlc_groups": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "hg_debug_msgs_rlc_points": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "hg_aggregate_pk": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "hg_combine_g1": (_I, [_P, _P, _P, _SZ, _P, _P]),
     "hg_combine_g2": (_I, [_P, _P, _P, _SZ, _P, _P]),

@@ -62,6 +62,14 @@ void launch_rlc_gt(const Gt* x, const int32_t* codes, const uint64_t* r, int n, 
                    Gt* z, hipStream_t s);
 // hdr: groups with a live member, groups whose code is not HG_OK, their live members
 void launch_rlc_count(const int32_t* gcodes, const uint32_t* glive, int ngroups, RlcHdr* hdr, hipStream_t s);
+// check i is a live member of a group that failed
+HG_DEV bool rlc_failed_member(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group, int i) {
+  return i < n && codes[i] == HG_OK && gcodes[(uint32_t)i / group] != HG_OK;
+}
+// bcount[b] = the failed groups' live members before block b of 256 checks
+// (ceil(n / 256) words): what a gather kernel ranks its members by
+void launch_rlc_failed_scan(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group, uint32_t* bcount,
+                            hipStream_t s);
 // The live members of the failed groups, in index order, into compact arrays
 // (m = hdr's failed_members entries): idx[j] = the check, csigs its marshal, cy
 // its fold value, ccodes[j] = HG_OK. bcount: ceil(n / 256) words of workspace.

@@ -219,9 +219,6 @@ __global__ __launch_bounds__(256) void k_rlc_count(const int32_t* gcodes, const 
     atomicAdd(&hdr->failed_members, live);
   }
 }
-HG_DEV bool rlc_failed_member(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group, int i) {
-  return i < n && codes[i] == HG_OK && gcodes[(uint32_t)i / group] != HG_OK;
-}
 __global__ __launch_bounds__(256) void k_rlc_bcount(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group,
                                                     uint32_t* bcount) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -298,14 +295,19 @@ void launch_rlc_gt(const Gt* x, const int32_t* codes, const uint64_t* r, int n, 
 void launch_rlc_count(const int32_t* gcodes, const uint32_t* glive, int ngroups, RlcHdr* hdr, hipStream_t s) {
   if (ngroups > 0) k_rlc_count<<<nblk(ngroups, 256), 256, 0, s>>>(gcodes, glive, ngroups, hdr);
 }
-void launch_rlc_gather(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group, const uint8_t* sigs,
-                       const Gt* y, uint32_t* bcount, uint32_t* idx, uint8_t* csigs, Gt* cy, int32_t* ccodes,
-                       hipStream_t s) {
+void launch_rlc_failed_scan(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group, uint32_t* bcount,
+                            hipStream_t s) {
   if (n <= 0) return;
   const int nb = nblk(n, 256);
   k_rlc_bcount<<<nb, 256, 0, s>>>(codes, gcodes, n, group, bcount);
   k_rlc_scan<<<1, 256, 0, s>>>(bcount, nb);
-  k_rlc_gather<<<nb, 256, 0, s>>>(codes, gcodes, n, group, sigs, y, bcount, idx, csigs, cy, ccodes);
+}
+void launch_rlc_gather(const int32_t* codes, const int32_t* gcodes, int n, uint32_t group, const uint8_t* sigs,
+                       const Gt* y, uint32_t* bcount, uint32_t* idx, uint8_t* csigs, Gt* cy, int32_t* ccodes,
+                       hipStream_t s) {
+  if (n <= 0) return;
+  launch_rlc_failed_scan(codes, gcodes, n, group, bcount, s);
+  k_rlc_gather<<<nblk(n, 256), 256, 0, s>>>(codes, gcodes, n, group, sigs, y, bcount, idx, csigs, cy, ccodes);
 }
 void launch_rlc_scatter(const uint32_t* idx, const int32_t* ccodes, int m, int32_t* codes, hipStream_t s) {
   if (m > 0) k_rlc_scatter<<<nblk(m, 256), 256, 0, s>>>(idx, ccodes, m, codes);

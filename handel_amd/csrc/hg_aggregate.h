@@ -1,8 +1,8 @@
 // hg_aggregate.h — the internal interface of aggregate verification: what
 // hg_gttables.cpp (the GT tables), hg_aggregate.cpp (a batch's workspaces, flows,
 // staging and entry points), hg_lanes.cpp (the service lanes), hg_rlc.cpp (the
-// random-linear-combination form) and hg_msgs.cpp (a message per request) use
-// of each other. Every name below has users in at least two of them.
+// random-linear-combination form), hg_msgs.cpp (a message per request) and
+// hg_msgs_rlc.cpp (its combined form) use of each other. Every name below has users in at least two of them.
 #pragma once
 #include "hg_ctx.h"
 
@@ -27,6 +27,8 @@ static constexpr int kNoMem = -1;
 int gt_submission_level(hg_ctx* c, size_t n);
 // builds up to `level` on stream s, lowering it (and the context's cap) to what the device and the budget hold
 int build_fitting_locked(hg_ctx* c, hipStream_t s, int& level);
+// the registry's G2 membership count into c->reg_non_g2, waiting for its check if still running
+int resolve_subgroup(hg_ctx* c);
 
 // ---------------------------------------------------------------- hg_aggregate.cpp
 // capacity of a batch's term and chunk lists
@@ -122,3 +124,16 @@ struct HostStage {
 // VerifyMultiSignature's requests: the range [0, N) with the multisignature's own bit count
 std::vector<hg_request> multisig_requests(const hg_ctx* c, const uint32_t* bitlens, const uint32_t* word_offsets,
                                           size_t n);
+
+// ---------------------------------------------------------------- hg_msgs.cpp
+// the G1 base table of launch_hash_points, built on stream s by the context's first call that needs it
+int ensure_g1_table(hg_ctx* c, hipStream_t s);
+// the host variants' argument check: every message range inside the pool (HG_ERR_ARG, the message named)
+int check_ranges(hg_ctx* c, const char* who, size_t pool_len, const uint32_t* off, const uint32_t* len, size_t n);
+// pool, offsets and lengths into c->msgs (c->stream, inside the caller's submission)
+int stage_messages(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* off, const uint32_t* len,
+                   size_t n);
+// hg_verify_aggregate_msgs_device's batch on stream s: the exact path (d_agg nullable)
+int aggregate_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_off,
+                                 const uint32_t* d_len, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
+                                 const uint8_t* d_sigs, int32_t* d_codes, uint8_t* d_agg, hipStream_t s);

@@ -4,7 +4,8 @@
 // (context, message, registry, single checks), hg_gttables.cpp (GT tables),
 // hg_aggregate.cpp (aggregate verification), hg_lanes.cpp (service lanes),
 // hg_rlc.cpp (its random-linear-combination form), hg_intake.cpp (packets,
-// stores) and hg_msgs.cpp (checks on their own messages) include it. Every
+// stores), hg_msgs.cpp (checks on their own messages) and hg_msgs_rlc.cpp
+// (their random-linear-combination form) include it. Every
 // device resource below is held by an owner of hg_dev.h, so deleting a
 // context, a lane or a store set frees what it holds.
 #pragma once
@@ -19,6 +20,7 @@
 
 #include "bn256_gt.h"
 #include "bn256_kernels.h"
+#include "bn256_mrlc.h"
 #include "bn256_rlc.h"
 #include "bn256_sigpair.h"
 #include "hg_codes.h"
@@ -93,8 +95,20 @@ struct MsgWs {
   DevBuf<PointG1> h;         // H per check
   DevBuf<uint8_t> pool;      // the host variants' staging: messages,
   DevBuf<uint32_t> off, len; // their offsets and lengths
+  // hg_verify_aggregate_msgs_rlc* (hg_msgs_rlc.cpp, bn256_msgsrlc.hip): per
+  // request r_i k_i mod Order, r_i H_i, the scaled check record and the Miller
+  // value; per group its first live member; and, grown only when a group
+  // fails, the recheck's compact check records and their H
+  DevBuf<uint32_t> rk;
+  DevBuf<PointG1> rh;
+  DevBuf<CheckIn> rchecks;
+  DevBuf<Gt> f;
+  DevBuf<uint32_t> carrier;
+  DevBuf<CheckIn> cchecks;
+  DevBuf<PointG1> ch;
   size_t bytes() const {
-    return g1_tab.bytes() + k.bytes() + hcodes.bytes() + h.bytes() + pool.bytes() + off.bytes() + len.bytes();
+    return g1_tab.bytes() + k.bytes() + hcodes.bytes() + h.bytes() + pool.bytes() + off.bytes() + len.bytes() +
+           rk.bytes() + rh.bytes() + rchecks.bytes() + f.bytes() + carrier.bytes() + cchecks.bytes() + ch.bytes();
   }
 };
 
@@ -192,7 +206,8 @@ struct hg_ctx {
   // the context's own aggregate submissions: padded, the two-wave form up to
   // kSigW2MaxN; overlap: hg_set_fold_overlap (HG_GT_OVERLAP=0 gives new contexts false)
   SigPolicy pol;
-  // hg_rlc_stats: the last hg_verify_aggregate_rlc* call's groups checked, groups failed, checks re-verified
+  // hg_rlc_stats: the last hg_verify_aggregate_rlc* or hg_verify_*_msgs_rlc* call's groups checked, groups
+  // failed, checks re-verified
   uint64_t rlc_stats[3] = {0, 0, 0};
   bool verify_split = false;  // hg_set_verify_split; HG_VERIFY_SPLIT=1 gives new contexts true
   // submission order across streams: the event recorded after the last

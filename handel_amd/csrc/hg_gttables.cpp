@@ -40,7 +40,7 @@ int gt_forced_level() {
   return lvl;
 }
 // the registry's G2 membership count, waiting for its check if still running
-static int resolve_subgroup(hg_ctx* c) {
+int resolve_subgroup(hg_ctx* c) {
   if (!c->sub_pending) return HG_OK;
   int cnt = 0;
   HG_CHECK(c, hipEventSynchronize(c->ev_sub));

@@ -15,7 +15,7 @@
 
 // the G1 base table, built by the context's first multi-message submission
 // (inside it: later submissions on other streams wait for this one's event)
-static int ensure_g1_table(hg_ctx* c, hipStream_t s) {
+int ensure_g1_table(hg_ctx* c, hipStream_t s) {
   if (c->msgs.g1_tab.p) return HG_OK;
   HG_CHECK(c, c->msgs.g1_tab.alloc(kG1TabEntries));
   launch_g1_base_table(c->msgs.g1_tab.p, s);
@@ -66,8 +66,7 @@ static int verify_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t po
 }
 
 // the host variants' argument check: every range inside the pool
-static int check_ranges(hg_ctx* c, const char* who, size_t pool_len, const uint32_t* off, const uint32_t* len,
-                        size_t n) {
+int check_ranges(hg_ctx* c, const char* who, size_t pool_len, const uint32_t* off, const uint32_t* len, size_t n) {
   if (pool_len >= ((uint64_t)1 << 32)) {
     c->err = std::string(who) + ": pool_len must be below 2^32";
     return HG_ERR_ARG;
@@ -84,8 +83,8 @@ static int check_ranges(hg_ctx* c, const char* who, size_t pool_len, const uint3
 }
 
 // pool, offsets and lengths to the device (c->stream, inside the caller's submission)
-static int stage_messages(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* off, const uint32_t* len,
-                          size_t n) {
+int stage_messages(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* off, const uint32_t* len,
+                   size_t n) {
   HG_CHECK(c, c->msgs.pool.ensure(pool_len));
   HG_CHECK(c, c->msgs.off.ensure(n));
   HG_CHECK(c, c->msgs.len.ensure(n));
@@ -110,10 +109,9 @@ static int stage_messages(hg_ctx* c, const uint8_t* pool, size_t pool_len, const
 // hg_set_verify_split says: the split form's Miller kernel ran 1.20 ms in
 // bn256_msgs.hip's unit against 0.75 ms for identical code elsewhere, cause not
 // found, so this path does not offer it.
-static int aggregate_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_off,
-                                        const uint32_t* d_len, const hg_request* d_reqs, size_t n,
-                                        const uint64_t* d_words, const uint8_t* d_sigs, int32_t* d_codes,
-                                        uint8_t* d_agg, hipStream_t s) {
+int aggregate_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_off,
+                                 const uint32_t* d_len, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
+                                 const uint8_t* d_sigs, int32_t* d_codes, uint8_t* d_agg, hipStream_t s) {
   if (c->nreg == 0) {
     c->err = "hg_verify_aggregate_msgs: needs a registry";
     return HG_ERR_ARG;

@@ -493,6 +493,108 @@ class Engine:
                                                        _ptr(codes)), "hg_verify_multisig_msgs")
         return codes
 
+    # ----------------------------------------------------------- ... one final exponentiation per group
+    def verify_aggregate_msgs_rlc_pool(self, pool, msg_off, msg_len, reqs: np.ndarray, words: np.ndarray,
+                                       sigs: bytes, seed: Optional[bytes] = None, group: int = RLC_GROUP):
+        """hg_verify_aggregate_msgs_rlc on a caller-built pool."""
+        pool, s = _u8(pool), _u8(sigs)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        ln = np.ascontiguousarray(msg_len, dtype=np.uint32)
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        sd = self._seed(seed)
+        n = len(reqs)
+        if len(s) != 64 * n or len(off) != n or len(ln) != n:
+            raise ValueError("one message range and 64 signature bytes per request")
+        codes = np.zeros(n, dtype=np.int32)
+        self._check(self.L.hg_verify_aggregate_msgs_rlc(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                        _ptr(off) if n else None, _ptr(ln) if n else None,
+                                                        _ptr(reqs) if n else None, n,
+                                                        _ptr(words) if len(words) else None, len(words),
+                                                        _ptr(s) if n else None, _ptr(sd), int(group),
+                                                        _ptr(codes) if n else None),
+                    "hg_verify_aggregate_msgs_rlc")
+        return codes
+
+    def verify_aggregate_msgs_rlc(self, msgs: Sequence[bytes], reqs: np.ndarray, words: np.ndarray, sigs: bytes,
+                                  seed: Optional[bytes] = None, group: int = RLC_GROUP) -> np.ndarray:
+        """verify_aggregate_msgs (codes only) with one final exponentiation per
+        `group` requests under random coefficients (hg_verify_aggregate_msgs_rlc):
+        the same codes, an invalid signature accepted with probability <= 2^-64
+        over `seed`, which the signatures' sender must not predict (None:
+        os.urandom(32)). rlc_stats() reports on the call."""
+        pool, off, ln = self.pack_messages(msgs)
+        return self.verify_aggregate_msgs_rlc_pool(pool, off, ln, reqs, words, sigs, seed, group)
+
+    def verify_aggregate_msgs_rlc_device(self, d_pool: int, pool_len: int, d_msg_off: int, d_msg_len: int,
+                                         d_reqs: int, n: int, d_words: int, d_sigs: int, d_codes: int,
+                                         seed: Optional[bytes] = None, group: int = RLC_GROUP,
+                                         stream: int = 0) -> None:
+        """hg_verify_aggregate_msgs_rlc_device on raw device pointers; synchronises
+        `stream` once (the failed groups' member count sizes their exact recheck)."""
+        sd = self._seed(seed)
+        self._check(self.L.hg_verify_aggregate_msgs_rlc_device(self.ctx, d_pool or None, pool_len, d_msg_off,
+                                                               d_msg_len, d_reqs, n, d_words or None, d_sigs,
+                                                               _ptr(sd), int(group), d_codes, stream or None),
+                    "hg_verify_aggregate_msgs_rlc_device")
+
+    def verify_multisig_msgs_rlc(self, msgs: Sequence[bytes], bitlens, word_offsets, words: np.ndarray, sigs: bytes,
+                                 seed: Optional[bytes] = None, group: int = RLC_GROUP) -> np.ndarray:
+        """verify_multisig_msgs with one final exponentiation per `group`
+        multisignatures (hg_verify_multisig_msgs_rlc)."""
+        pool, off, ln = self.pack_messages(msgs)
+        bl = np.ascontiguousarray(bitlens, dtype=np.uint32)
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint32)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        s = _u8(sigs)
+        sd = self._seed(seed)
+        n = len(bl)
+        if len(s) != 64 * n or len(off) != n or len(wo) != n:
+            raise ValueError("one message, one word offset and 64 signature bytes per multisignature")
+        codes = np.zeros(n, dtype=np.int32)
+        self._check(self.L.hg_verify_multisig_msgs_rlc(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                       _ptr(off) if n else None, _ptr(ln) if n else None,
+                                                       _ptr(bl) if n else None, _ptr(wo) if n else None, n,
+                                                       _ptr(words) if len(words) else None, len(words),
+                                                       _ptr(s) if n else None, _ptr(sd), int(group),
+                                                       _ptr(codes) if n else None), "hg_verify_multisig_msgs_rlc")
+        return codes
+
+    def debug_msgs_rlc_groups(self, msgs: Sequence[bytes], reqs: np.ndarray, words: np.ndarray, sigs: bytes, coeffs,
+                              group: int):
+        """The combination up to the group verdicts with the given coefficients
+        (hg_debug_msgs_rlc_groups): (codes, group_codes, group_live)."""
+        pool, off, ln = self.pack_messages(msgs)
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        s = _u8(sigs)
+        n = len(reqs)
+        k = np.ascontiguousarray(np.array([int(c) for c in coeffs], dtype=np.uint64))
+        assert len(k) == n and len(off) == n
+        ng = (n + group - 1) // group
+        codes = np.zeros(n, dtype=np.int32)
+        gcodes = np.zeros(ng, dtype=np.int32)
+        glive = np.zeros(ng, dtype=np.uint32)
+        self._check(self.L.hg_debug_msgs_rlc_groups(self.ctx, _ptr(pool) if len(pool) else None, len(pool), _ptr(off),
+                                                    _ptr(ln), _ptr(reqs), n, _ptr(words) if len(words) else None,
+                                                    len(words), _ptr(s), _ptr(k), int(group), _ptr(codes),
+                                                    _ptr(gcodes), _ptr(glive)), "hg_debug_msgs_rlc_groups")
+        return codes, gcodes, glive
+
+    def debug_msgs_rlc_points(self, msgs: Sequence[bytes], coeffs) -> bytes:
+        """Per message the marshal of coeffs[i] hashedMessage(msgs[i]), zeros where
+        the message cannot be hashed (hg_debug_msgs_rlc_points)."""
+        pool, off, ln = self.pack_messages(msgs)
+        n = len(off)
+        k = np.ascontiguousarray(np.array([int(c) for c in coeffs], dtype=np.uint64))
+        assert len(k) == n
+        out = np.zeros(64 * n, dtype=np.uint8)
+        if n:
+            self._check(self.L.hg_debug_msgs_rlc_points(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                        _ptr(off), _ptr(ln), _ptr(k), n, _ptr(out)),
+                        "hg_debug_msgs_rlc_points")
+        return out.tobytes()
+
     def verify_aggregate_device(self, d_reqs: int, n: int, d_words: int, d_sigs: int, d_codes: int,
                                 d_agg: int = 0, stream: int = 0):
         self._check(self.L.hg_verify_aggregate_device(self.ctx, d_reqs, n, d_words, d_sigs, d_codes,

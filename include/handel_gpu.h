@@ -357,6 +357,63 @@ int hg_debug_rlc_groups(hg_ctx* ctx, const hg_request* reqs, size_t n, const uin
                         const uint8_t* sigs, const uint64_t* coeffs, uint32_t group, int32_t* codes,
                         int32_t* group_codes, uint32_t* group_live);
 
+/* ---------------------------------------------------------------- ... with a message per request
+ * hg_verify_aggregate_msgs (verdicts only: no agg_pk_out, the exact call serves
+ * callers who want the keys) with the final exponentiations of `group`
+ * requests at a time replaced by one (processing.go:342-368 verifySignature;
+ * crypto.go:120-137 VerifyMultiSignature(msg, ms, reg, cons) with the message
+ * per call). GT tables hold e(H, pk_i) for one H and cannot help here; for the
+ * live requests i of a group, with agg_i the aggregate key of request i,
+ *     prod e(r_i H_i, agg_i) * e(-sum r_i sig_i, G2Base) == 1
+ * holds when every check holds, and with probability <= 2^-64 over the
+ * coefficients when one does not: a request costs one Miller loop and one Fp12
+ * product, a group one final exponentiation. Messages, argument rules and
+ * per-request precedence are hg_verify_aggregate_msgs*'s; seed, r_i and group
+ * are hg_verify_aggregate_rlc's (NULL seed, group == 0 or group > 4096:
+ * HG_ERR_ARG; n = 0: HG_OK). A request is live when everything decided before
+ * the pairing left it HG_OK (unmarshal, level, hash, empty aggregate); an
+ * infinity signature on a non-empty set is live and fails its group. The live
+ * members of a group that fails are verified again one by one on the exact
+ * call's path, so every code is hg_verify_aggregate_msgs's, except that an
+ * invalid signature is accepted with probability <= 2^-64 over `seed`.
+ * The combination runs when every registry key is proven to lie in G2
+ * (hg_registry_non_g2 == 0; the call waits for a membership check still
+ * running); otherwise, and above 2^28 requests, the call is
+ * hg_verify_aggregate_msgs_device's path as it stands and hg_rlc_stats reports
+ * zeros. Like the exact calls these need a registry and no hg_set_message, and
+ * neither read nor change the context's messages, their H, the GT tables, their
+ * level or the request count of the table policy. Each call that runs the
+ * combination synchronises its stream once and reads 16 bytes back, the
+ * _device form included. hg_rlc_stats reports on these calls too. */
+int hg_verify_aggregate_msgs_rlc(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                                 const uint32_t* msg_len, const hg_request* reqs, size_t n, const uint64_t* words,
+                                 size_t nwords, const uint8_t* sigs, const uint8_t seed[32], uint32_t group,
+                                 int32_t* codes);
+int hg_verify_aggregate_msgs_rlc_device(hg_ctx* ctx, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
+                                        const uint32_t* d_msg_len, const hg_request* d_reqs, size_t n,
+                                        const uint64_t* d_words, const uint8_t* d_sigs, const uint8_t seed[32],
+                                        uint32_t group, int32_t* d_codes, void* stream);
+/* VerifyMultiSignature(msg_i, ms_i, reg, cons) x n (crypto.go:120-137) in the
+ * combined form: hg_verify_multisig_msgs's requests and its rename of
+ * HG_ERR_LEVEL to HG_ERR_MULTI_SIZES (processing.go:342-368 for the rest). */
+int hg_verify_multisig_msgs_rlc(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                                const uint32_t* msg_len, const uint32_t* bitlens, const uint32_t* word_offsets,
+                                size_t n, const uint64_t* words, size_t nwords, const uint8_t* sigs,
+                                const uint8_t seed[32], uint32_t group, int32_t* codes);
+/* probes with caller-given coefficients (tests only; never use for verification).
+ * hg_debug_msgs_rlc_groups: everything up to the group verdicts, no recheck:
+ * codes[n] = what is decided before the pairing, group_codes[g] = HG_OK or
+ * HG_ERR_SIG_INVALID, group_live[g] = group g's live members. HG_ERR_ARG when
+ * the context would not run the combination.
+ * hg_debug_msgs_rlc_points: out[64 i ..] = the G1 marshal of
+ * coeffs[i] hashedMessage(msg_i); zeros where the message cannot be hashed. */
+int hg_debug_msgs_rlc_groups(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                             const uint32_t* msg_len, const hg_request* reqs, size_t n, const uint64_t* words,
+                             size_t nwords, const uint8_t* sigs, const uint64_t* coeffs, uint32_t group,
+                             int32_t* codes, int32_t* group_codes, uint32_t* group_live);
+int hg_debug_msgs_rlc_points(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                             const uint32_t* msg_len, const uint64_t* coeffs, size_t n, uint8_t* out);
+
 /* Batched PublicKey.Combine fold only: n requests -> n*128 B aggregate keys
  * (bn256/go/bn256.go:97-105). codes: HG_OK, HG_ERR_LEVEL or HG_ERR_EMPTY_AGG. */
 int hg_aggregate_pk(hg_ctx* ctx, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
