@@ -436,6 +436,83 @@ func (e *Engine) RLCStats() (groups, groupsFailed, rechecked uint64) {
 	return uint64(g), uint64(f), uint64(r)
 }
 
+// VerifyBatchRLC is n = len(sigs)/64 independent PublicKey.VerifySignature
+// checks (bn256/go/bn256.go:82-94) on the message of the last SetMessage, with
+// the final exponentiations of `group` checks at a time replaced by one under
+// random coefficients from crypto/rand (hg_verify_batch_rlc): the same code per
+// check as hg_verify_batch, except that an invalid signature is accepted with
+// probability at most 2^-64. The keys may be any points G2.Unmarshal accepts
+// (bn256/go/bn256.go:113-120): every check's Miller loop also decides whether
+// its key lies in G2, and a group that holds a key that does not is verified
+// check by check. The form pays off on large batches that are almost all
+// valid; BatchRLCStats reports on the call. group <= 0 selects DefaultRLCGroup;
+// the largest group is 4096.
+func (e *Engine) VerifyBatchRLC(pks, sigs []byte, group int) ([]int32, error) {
+	n := len(sigs) / 64
+	if len(sigs) != 64*n || len(pks) != 128*n {
+		return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyBatchRLC: pks/sigs sizes"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	if group <= 0 {
+		group = DefaultRLCGroup
+	}
+	seed, err := rlcSeed()
+	if err != nil {
+		return nil, err
+	}
+	codes := failedCodes(n)
+	rc := C.hg_verify_batch_rlc(e.ctx, bytePtr(pks), bytePtr(sigs), C.size_t(n), (*C.uint8_t)(unsafe.Pointer(&seed[0])),
+		C.uint32_t(group), codePtr(codes))
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
+	}
+	return codes, nil
+}
+
+// VerifyBatchMsgsRLC is VerifyBatchMsgs in the same form
+// (hg_verify_batch_msgs_rlc): n = len(msgs) checks, each on its own message
+// (bn256/go/bn256.go:82-94), one final exponentiation per group. The context's
+// current message and its tables stay as they are.
+func (e *Engine) VerifyBatchMsgsRLC(msgs [][]byte, pks, sigs []byte, group int) ([]int32, error) {
+	n := len(msgs)
+	if len(sigs) != 64*n || len(pks) != 128*n {
+		return nil, &DeviceError{Code: C.HG_ERR_ARG, Msg: "VerifyBatchMsgsRLC: msgs/pks/sigs sizes"}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	if group <= 0 {
+		group = DefaultRLCGroup
+	}
+	seed, err := rlcSeed()
+	if err != nil {
+		return nil, err
+	}
+	pool, off, ln, err := packMessages("VerifyBatchMsgsRLC", msgs)
+	if err != nil {
+		return nil, err
+	}
+	codes := failedCodes(n)
+	rc := C.hg_verify_batch_msgs_rlc(e.ctx, bytePtr(pool), C.size_t(len(pool)), (*C.uint32_t)(unsafe.Pointer(&off[0])),
+		(*C.uint32_t)(unsafe.Pointer(&ln[0])), bytePtr(pks), bytePtr(sigs), C.size_t(n),
+		(*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint32_t(group), codePtr(codes))
+	if rc != C.HG_OK {
+		return nil, e.fail(rc)
+	}
+	return codes, nil
+}
+
+// BatchRLCStats reports the last VerifyBatch*RLC call: groups checked, groups
+// that failed, checks verified again one by one, and live checks whose key was
+// not proven to lie in G2 (hg_batch_rlc_stats).
+func (e *Engine) BatchRLCStats() (groups, groupsFailed, rechecked, nonG2 uint64) {
+	var g, f, r, m C.uint64_t
+	C.hg_batch_rlc_stats(e.ctx, &g, &f, &r, &m)
+	return uint64(g), uint64(f), uint64(r), uint64(m)
+}
+
 // AggregateKeys is the Combine fold alone: the marshalled aggregate public
 // key of every request (codes: HG_OK, HG_ERR_LEVEL or HG_ERR_EMPTY_AGG).
 func (e *Engine) AggregateKeys(reqs []Request) ([]byte, []int32, error) {

@@ -117,6 +117,13 @@ SIGNATURES = {
     "hg_verify_multisig_msgs_rlc": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P]),
     "hg_debug_msgs_rlc_groups": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _SZ, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "hg_debug_msgs_rlc_points": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "hg_verify_batch_rlc": (_I, [_P, _P, _P, _SZ, _P, ctypes.c_uint32, _P]),
+    "hg_verify_batch_rlc_device": (_I, [_P, _P, _P, _SZ, _P, ctypes.c_uint32, _P, _P]),
+    "hg_verify_batch_msgs_rlc": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, ctypes.c_uint32, _P]),
+    "hg_verify_batch_msgs_rlc_device": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, ctypes.c_uint32, _P, _P]),
+    "hg_batch_rlc_stats": (_I, [_P] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
+    "hg_debug_g2_member": (_I, [_P, _P, _SZ, _P, _P]),
+    "hg_debug_batch_rlc_groups": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, ctypes.c_uint32, _P, _P, _P]),
     "hg_aggregate_pk": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "hg_combine_g1": (_I, [_P, _P, _P, _SZ, _P, _P]),
     "hg_combine_g2": (_I, [_P, _P, _P, _SZ, _P, _P]),

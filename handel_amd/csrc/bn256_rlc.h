@@ -41,7 +41,7 @@ struct RlcHdr {
   uint32_t failed_members;  // live members of the groups that failed: the recheck's size
   uint32_t groups;          // groups with a live member
   uint32_t groups_failed;
-  uint32_t pad;
+  uint32_t pad;  // hg_verify_batch_rlc* (bn256_brlc.h): live checks whose key is not a proven member of G2
 };
 struct Gt;
 

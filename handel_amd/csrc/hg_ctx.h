@@ -5,7 +5,8 @@
 // hg_aggregate.cpp (aggregate verification), hg_lanes.cpp (service lanes),
 // hg_rlc.cpp (its random-linear-combination form), hg_intake.cpp (packets,
 // stores), hg_msgs.cpp (checks on their own messages) and hg_msgs_rlc.cpp
-// (their random-linear-combination form) include it. Every
+// (their random-linear-combination form) and hg_batch_rlc.cpp (independent
+// checks in that form) include it. Every
 // device resource below is held by an owner of hg_dev.h, so deleting a
 // context, a lane or a store set frees what it holds.
 #pragma once
@@ -106,9 +107,13 @@ struct MsgWs {
   DevBuf<uint32_t> carrier;
   DevBuf<CheckIn> cchecks;
   DevBuf<PointG1> ch;
+  // hg_verify_batch_rlc*, hg_verify_batch_msgs_rlc* (hg_batch_rlc.cpp): the
+  // G2 membership verdict of every check's key (bn256_batchrlc.hip)
+  DevBuf<uint32_t> member;
   size_t bytes() const {
     return g1_tab.bytes() + k.bytes() + hcodes.bytes() + h.bytes() + pool.bytes() + off.bytes() + len.bytes() +
-           rk.bytes() + rh.bytes() + rchecks.bytes() + f.bytes() + carrier.bytes() + cchecks.bytes() + ch.bytes();
+           rk.bytes() + rh.bytes() + rchecks.bytes() + f.bytes() + carrier.bytes() + cchecks.bytes() + ch.bytes() +
+           member.bytes();
   }
 };
 
@@ -209,6 +214,8 @@ struct hg_ctx {
   // hg_rlc_stats: the last hg_verify_aggregate_rlc* or hg_verify_*_msgs_rlc* call's groups checked, groups
   // failed, checks re-verified
   uint64_t rlc_stats[3] = {0, 0, 0};
+  // hg_batch_rlc_stats: the last hg_verify_batch*_rlc* call's live checks whose key was not proven in G2
+  uint64_t brlc_non_g2 = 0;
   bool verify_split = false;  // hg_set_verify_split; HG_VERIFY_SPLIT=1 gives new contexts true
   // submission order across streams: the event recorded after the last
   // submission and the stream it ran on (the workspaces above are shared)

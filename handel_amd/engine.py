@@ -334,6 +334,115 @@ class Engine:
         self._check(self.L.hg_rlc_stats(self.ctx, *[ctypes.byref(x) for x in v]), "hg_rlc_stats")
         return tuple(int(x.value) for x in v)
 
+    # ------------------------------------------------------------ ... of independent checks on arbitrary keys
+    def verify_batch_rlc(self, pks: bytes, sigs: bytes, seed: Optional[bytes] = None,
+                         group: int = RLC_GROUP) -> np.ndarray:
+        """verify_batch with one final exponentiation per `group` checks under
+        random coefficients (hg_verify_batch_rlc): the same codes, an invalid
+        signature accepted with probability <= 2^-64 over `seed`, which the
+        signatures' sender must not predict (None: os.urandom(32)). Each
+        check's Miller loop also decides whether its key lies in G2; a group
+        holding a key that does not is verified check by check.
+        batch_rlc_stats() reports on the call."""
+        a, b = _u8(pks), _u8(sigs)
+        n = len(b) // 64
+        if len(a) != 128 * n:
+            raise ValueError("pks must hold 128 bytes per signature")
+        sd = self._seed(seed)
+        codes = np.zeros(n, dtype=np.int32)
+        self._check(self.L.hg_verify_batch_rlc(self.ctx, _ptr(a) if n else None, _ptr(b) if n else None, n, _ptr(sd),
+                                               int(group), _ptr(codes) if n else None), "hg_verify_batch_rlc")
+        return codes
+
+    def verify_batch_rlc_device(self, d_pks: int, d_sigs: int, n: int, d_codes: int, seed: Optional[bytes] = None,
+                                group: int = RLC_GROUP, stream: int = 0) -> None:
+        """hg_verify_batch_rlc_device on raw device pointers; synchronises
+        `stream` once (the failed groups' member count sizes their recheck)."""
+        sd = self._seed(seed)
+        self._check(self.L.hg_verify_batch_rlc_device(self.ctx, d_pks, d_sigs, n, _ptr(sd), int(group), d_codes,
+                                                      stream or None), "hg_verify_batch_rlc_device")
+
+    def verify_batch_msgs_rlc_pool(self, pool, msg_off, msg_len, pks: bytes, sigs: bytes,
+                                   seed: Optional[bytes] = None, group: int = RLC_GROUP) -> np.ndarray:
+        """hg_verify_batch_msgs_rlc on a caller-built pool."""
+        pool, a, b = _u8(pool), _u8(pks), _u8(sigs)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        ln = np.ascontiguousarray(msg_len, dtype=np.uint32)
+        n = len(b) // 64
+        if len(a) != 128 * n or len(off) != n or len(ln) != n:
+            raise ValueError("one message range, 128 key bytes and 64 signature bytes per check")
+        sd = self._seed(seed)
+        codes = np.zeros(n, dtype=np.int32)
+        self._check(self.L.hg_verify_batch_msgs_rlc(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                    _ptr(off) if n else None, _ptr(ln) if n else None,
+                                                    _ptr(a) if n else None, _ptr(b) if n else None, n, _ptr(sd),
+                                                    int(group), _ptr(codes) if n else None),
+                    "hg_verify_batch_msgs_rlc")
+        return codes
+
+    def verify_batch_msgs_rlc(self, msgs: Sequence[bytes], pks: bytes, sigs: bytes, seed: Optional[bytes] = None,
+                              group: int = RLC_GROUP) -> np.ndarray:
+        """verify_batch_msgs with one final exponentiation per `group` checks
+        under random coefficients (hg_verify_batch_msgs_rlc): the same codes;
+        seed and membership as verify_batch_rlc."""
+        pool, off, ln = self.pack_messages(msgs)
+        return self.verify_batch_msgs_rlc_pool(pool, off, ln, pks, sigs, seed, group)
+
+    def verify_batch_msgs_rlc_device(self, d_pool: int, pool_len: int, d_msg_off: int, d_msg_len: int, d_pks: int,
+                                     d_sigs: int, n: int, d_codes: int, seed: Optional[bytes] = None,
+                                     group: int = RLC_GROUP, stream: int = 0) -> None:
+        """hg_verify_batch_msgs_rlc_device on raw device pointers; synchronises
+        `stream` once; a range past pool_len gives that check HG_ERR_ARG."""
+        sd = self._seed(seed)
+        self._check(self.L.hg_verify_batch_msgs_rlc_device(self.ctx, d_pool or None, pool_len, d_msg_off, d_msg_len,
+                                                           d_pks, d_sigs, n, _ptr(sd), int(group), d_codes,
+                                                           stream or None), "hg_verify_batch_msgs_rlc_device")
+
+    def batch_rlc_stats(self) -> Tuple[int, int, int, int]:
+        """The last verify_batch*_rlc* call: (groups checked, groups that
+        failed, checks re-verified one by one, live checks whose key was not
+        proven in G2)."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        self._check(self.L.hg_batch_rlc_stats(self.ctx, *[ctypes.byref(x) for x in v]), "hg_batch_rlc_stats")
+        return tuple(int(x.value) for x in v)
+
+    def g2_members(self, pks: bytes) -> Tuple[np.ndarray, np.ndarray]:
+        """(flags, codes) of hg_debug_g2_member: the keys decoded by the
+        context's flavor, flags[i] = 1 where the membership Miller loop proves
+        key i in G2 (or it is the infinity key), 0 elsewhere."""
+        a = _u8(pks)
+        n = len(a) // 128
+        flags = np.zeros(n, dtype=np.uint32)
+        codes = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.L.hg_debug_g2_member(self.ctx, _ptr(a), n, _ptr(flags), _ptr(codes)),
+                        "hg_debug_g2_member")
+        return flags, codes
+
+    def debug_batch_rlc_groups(self, msgs: Optional[Sequence[bytes]], pks: bytes, sigs: bytes, coeffs, group: int):
+        """Everything up to the group verdicts with caller-given coefficients
+        (hg_debug_batch_rlc_groups): (codes, group_codes, group_live). msgs
+        None: every check on the context's message."""
+        a, b = _u8(pks), _u8(sigs)
+        k = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        n = len(b) // 64
+        if len(a) != 128 * n or len(k) != n or (msgs is not None and len(msgs) != n):
+            raise ValueError("one key, one signature, one coefficient (and one message) per check")
+        ng = (n + int(group) - 1) // int(group) if group else 0
+        codes = np.zeros(n, dtype=np.int32)
+        gcodes = np.zeros(ng, dtype=np.int32)
+        glive = np.zeros(ng, dtype=np.uint32)
+        if msgs is None:
+            pool, off, ln = np.zeros(0, dtype=np.uint8), None, None
+        else:
+            pool, off, ln = self.pack_messages(msgs)
+        self._check(self.L.hg_debug_batch_rlc_groups(self.ctx, _ptr(pool) if len(pool) else None, len(pool),
+                                                     _ptr(off) if off is not None else None,
+                                                     _ptr(ln) if ln is not None else None, _ptr(a), _ptr(b), n,
+                                                     _ptr(k), int(group), _ptr(codes), _ptr(gcodes), _ptr(glive)),
+                    "hg_debug_batch_rlc_groups")
+        return codes, gcodes, glive
+
     @staticmethod
     def debug_rlc_coeffs(seed: bytes, first: int, n: int) -> np.ndarray:
         """r_first .. r_(first+n-1) by the code the device runs (host only: no context, no GPU)."""

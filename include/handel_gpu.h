@@ -414,6 +414,67 @@ int hg_debug_msgs_rlc_groups(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, 
 int hg_debug_msgs_rlc_points(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
                              const uint32_t* msg_len, const uint64_t* coeffs, size_t n, uint8_t* out);
 
+/* ---------------------------------------------------------------- ... of independent checks on arbitrary keys
+ * hg_verify_batch and hg_verify_batch_msgs (n independent
+ * PublicKey.VerifySignature checks, bn256/go/bn256.go:82-94;
+ * simul/p2p/aggregator.go:244) with the final exponentiations of `group` checks
+ * at a time replaced by one. For the live checks i of a group, with H_i the
+ * context's H or the check's own,
+ *     prod e(r_i H_i, pk_i) * e(-sum r_i sig_i, G2Base) == 1
+ * holds when every check holds, and with probability <= 2^-64 over the
+ * coefficients when one does not, provided every pk_i lies in G2. The keys are
+ * arbitrary points of the twist (G2.Unmarshal, bn256/go/bn256.go:113-120), so
+ * each check's Miller loop also decides whether its key lies in G2 (the loop
+ * ends on [6u+2]Q + psi(Q) - psi^2(Q), which equals -psi^3(Q) exactly on G2;
+ * DESIGN.md §3n): a group that holds a live check whose key is not proven in G2
+ * counts as failed whatever its product. A check costs one Miller loop and one
+ * Fp12 product, a group one final exponentiation.
+ * hg_verify_batch_rlc* run on the context's current message, as
+ * hg_verify_batch (HG_ERR_ARG without hg_set_message); the codes are
+ * hg_verify_batch's, check for check. hg_verify_batch_msgs_rlc*: messages,
+ * argument rules, range checks and per-check precedence are
+ * hg_verify_batch_msgs*'s. seed, r_i and group are hg_verify_aggregate_rlc's
+ * (NULL seed, group == 0 or group > 4096: HG_ERR_ARG; n = 0: HG_OK). A check
+ * is live when everything decided before the pairing left it HG_OK (unmarshal,
+ * cf's subgroup check, hash); an infinity signature is live, a key at infinity
+ * is live and counts as a member. The live members of a group that fails are
+ * verified again one by one with the exact two-pairing check, so every code is
+ * the exact call's, except that an invalid signature is accepted with
+ * probability <= 2^-64 over `seed`. Above 2^28 checks the call is the exact
+ * call as it stands and the statistics are zeros. Each call that runs the
+ * combination synchronises its stream once and reads 16 bytes back, the _device
+ * forms included. */
+int hg_verify_batch_rlc(hg_ctx* ctx, const uint8_t* pks, const uint8_t* sigs, size_t n, const uint8_t seed[32],
+                        uint32_t group, int32_t* codes);
+int hg_verify_batch_rlc_device(hg_ctx* ctx, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n,
+                               const uint8_t seed[32], uint32_t group, int32_t* d_codes, void* stream);
+int hg_verify_batch_msgs_rlc(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                             const uint32_t* msg_len, const uint8_t* pks, const uint8_t* sigs, size_t n,
+                             const uint8_t seed[32], uint32_t group, int32_t* codes);
+int hg_verify_batch_msgs_rlc_device(hg_ctx* ctx, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
+                                    const uint32_t* d_msg_len, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n,
+                                    const uint8_t seed[32], uint32_t group, int32_t* d_codes, void* stream);
+/* last hg_verify_batch*_rlc* call on this context: groups, groups_failed and
+ * rechecked as hg_rlc_stats (which reports on these calls too); non_g2 = the
+ * live checks whose key was not proven to lie in G2 (each fails its group). */
+int hg_batch_rlc_stats(hg_ctx* ctx, uint64_t* groups, uint64_t* groups_failed, uint64_t* rechecked,
+                       uint64_t* non_g2);
+/* probes (tests only; never use for verification).
+ * hg_debug_g2_member: the keys decoded by the context's flavor
+ * (PublicKey.UnmarshalBinary, bn256/go/bn256.go:113-120; codes[i]), each run
+ * through the membership Miller loop with H the G1 generator: flags[i] = 1 for
+ * a key in G2 or at infinity, 0 for any other key and where the key does not
+ * decode.
+ * hg_debug_batch_rlc_groups: caller-given coefficients, everything up to the
+ * group verdicts, no recheck: codes[n] = what is decided before the pairing,
+ * group_codes[g] = HG_OK or HG_ERR_SIG_INVALID, group_live[g] = group g's live
+ * members. msg_off == msg_len == NULL: every check on the context's message. */
+int hg_debug_g2_member(hg_ctx* ctx, const uint8_t* pks, size_t n, uint32_t* flags, int32_t* codes);
+int hg_debug_batch_rlc_groups(hg_ctx* ctx, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
+                              const uint32_t* msg_len, const uint8_t* pks, const uint8_t* sigs, size_t n,
+                              const uint64_t* coeffs, uint32_t group, int32_t* codes, int32_t* group_codes,
+                              uint32_t* group_live);
+
 /* Batched PublicKey.Combine fold only: n requests -> n*128 B aggregate keys
  * (bn256/go/bn256.go:97-105). codes: HG_OK, HG_ERR_LEVEL or HG_ERR_EMPTY_AGG. */
 int hg_aggregate_pk(hg_ctx* ctx, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
