@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64) void k_brlc_members(const int32_t* codes, const
   for (int d = 32; d > 0; d >>= 1) bad += __shfl_xor(bad, d);
   if (lane == 0 && bad) {
     gcodes[g] = HG_ERR_SIG_INVALID;
-    atomicAdd(&hdr->pad, bad);
+    atomicAdd(&hdr->non_g2, bad);
   }
 }
 

@@ -27,7 +27,7 @@ void launch_brlc_one_message(BrlcScalar k1, const PointG1* h1, int32_t code, int
 void launch_brlc_miller(const CheckIn* in, int n, const LineCoef* tab, const PointG1* hpts, int hstride, Gt* f,
                         uint32_t* member, hipStream_t s);
 // A group that holds a check with codes[i] == HG_OK and member[i] == 0 fails:
-// gcodes[g] = HG_ERR_SIG_INVALID, and hdr->pad += the number of such checks.
+// gcodes[g] = HG_ERR_SIG_INVALID, and hdr->non_g2 += the number of such checks.
 void launch_brlc_members(const int32_t* codes, const uint32_t* member, int n, uint32_t group, int ngroups,
                          int32_t* gcodes, RlcHdr* hdr, hipStream_t s);
 // hg_debug_g2_member: out[i] = (pks[i], the infinity signature), the key at

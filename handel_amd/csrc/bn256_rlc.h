@@ -11,6 +11,10 @@ namespace hg {
 
 static constexpr uint32_t kRlcMaxGroup = 4096;
 static constexpr int kRlcBits = 64;  // bits of a coefficient: subset products per group
+// what every combined call (hg_rlc.cpp, hg_msgs_rlc.cpp, hg_batch_rlc.cpp) accepts as its group size
+inline bool rlc_group_ok(uint32_t group) { return group >= 1 && group <= kRlcMaxGroup; }
+// groups of a batch of n checks: the last one may be ragged
+inline size_t rlc_groups(size_t n, uint32_t group) { return (n + group - 1) / group; }
 
 // the first 8 digest bytes as a little-endian integer (h: the digest's big-endian
 // words); 0, which would drop the check from its group, becomes 1
@@ -32,6 +36,12 @@ HG_HD uint64_t rlc_coeff(const uint8_t seed[32], uint64_t i) {
 struct RlcSeed {
   uint8_t b[32];
 };
+// by value into launch_rlc_prep; seed == nullptr (a probe brings its coefficients): zeros
+inline RlcSeed rlc_seed_of(const uint8_t* seed) {
+  RlcSeed sd{};
+  for (int k = 0; seed && k < 32; k++) sd.b[k] = seed[k];
+  return sd;
+}
 // a G1 point in Jacobian coordinates between the two G1 kernels
 struct RlcJac {
   Fp x, y, z;
@@ -41,7 +51,7 @@ struct RlcHdr {
   uint32_t failed_members;  // live members of the groups that failed: the recheck's size
   uint32_t groups;          // groups with a live member
   uint32_t groups_failed;
-  uint32_t pad;  // hg_verify_batch_rlc* (bn256_brlc.h): live checks whose key is not a proven member of G2
+  uint32_t non_g2;  // hg_verify_batch_rlc* (bn256_brlc.h): live checks whose key is not a proven member of G2
 };
 struct Gt;
 

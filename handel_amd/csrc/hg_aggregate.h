@@ -1,9 +1,12 @@
 // hg_aggregate.h — the internal interface of aggregate verification: what
 // hg_gttables.cpp (the GT tables), hg_aggregate.cpp (a batch's workspaces, flows,
 // staging and entry points), hg_lanes.cpp (the service lanes), hg_rlc.cpp (the
-// random-linear-combination form), hg_msgs.cpp (a message per request) and
-// hg_msgs_rlc.cpp (its combined form) use of each other. Every name below has users in at least two of them.
+// random-linear-combination form), hg_msgs.cpp (a message per request),
+// hg_msgs_rlc.cpp (its combined form) and hg_batch_rlc.cpp (independent checks
+// in that form) use of each other. Every name below has users in at least two of them.
 #pragma once
+#include <optional>
+
 #include "hg_ctx.h"
 
 // internal return code: an allocation of the GT path failed (the caller falls back to a lower level)
@@ -125,6 +128,23 @@ struct HostStage {
 std::vector<hg_request> multisig_requests(const hg_ctx* c, const uint32_t* bitlens, const uint32_t* word_offsets,
                                           size_t n);
 
+// ---------------------------------------------------------------- hg_rlc.cpp
+// One combined call as its entry point asked for it (who: its name, for hg_last_error).
+struct RlcCall {
+  const char* who;
+  const uint8_t* seed;       // 32 bytes, or
+  const uint64_t* d_coeffs;  // the probes' coefficients (device)
+  uint32_t group;
+  bool recheck;  // false: a probe stops after the group verdicts
+};
+// hg_rlc_stats of a call that did not run the combination
+void rlc_clear_stats(hg_ctx* c);
+// The one read-back of a combined call: ws.rlc_hdr to *h on stream s, synchronised,
+// into c->rlc_stats; HG_ERR_DEVICE if it counts more failed members than the n checks.
+int rlc_read_stats(hg_ctx* c, const RlcCall& call, size_t n, hipStream_t s, RlcHdr* h);
+// the probes' copy-out of the ng groups' verdicts and live counts (stream s, not synchronised)
+int rlc_copy_groups(hg_ctx* c, size_t ng, int32_t* group_codes, uint32_t* group_live, hipStream_t s);
+
 // ---------------------------------------------------------------- hg_msgs.cpp
 // the G1 base table of launch_hash_points, built on stream s by the context's first call that needs it
 int ensure_g1_table(hg_ctx* c, hipStream_t s);
@@ -137,3 +157,37 @@ int stage_messages(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32
 int aggregate_msgs_device_locked(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_off,
                                  const uint32_t* d_len, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
                                  const uint8_t* d_sigs, int32_t* d_codes, uint8_t* d_agg, hipStream_t s);
+
+// ---------------------------------------------------------------- hg_msgs_rlc.cpp
+// The combined flow of n checks that carry a message each, on stream s with
+// the context's workspaces: this file's requests and hg_batch_rlc.cpp's
+// independent checks. hs is the side stream, or s with hg_set_fold_overlap(ctx, 0).
+//   s:  coefficients -> the caller's check records and codes ..... -> wait -> the caller's code merge -> G1 sums,
+//       scaled records, Miller loops, group products, FE, verdicts (members: G2 membership) (-> recheck)
+//   hs: wait -> the caller's H per check, k_mrlc_scalars, k_hash_points (r H) -> join
+// A caller runs, returning the first error as it stands:
+//   mrlc_begin;  on f.hs its H per check into c->msgs.k, hcodes and h;  mrlc_hashed;
+//   on s its check records into c->ws.checks and their codes;  mrlc_wait_hashed;
+//   on s its merge of c->msgs.hcodes into the codes;  mrlc_finish.
+struct MrlcFlow {
+  hg_ctx* c;
+  const RlcCall& call;
+  size_t n;
+  bool members;  // the Miller kernel also yields the G2 membership of every check's key (c->msgs.member)
+  hipStream_t s;
+  hipStream_t hs = nullptr;  // from mrlc_begin on
+  RlcHdr hdr{};              // the call's counters once mrlc_finish read them back (call.recheck)
+  Submission sub;
+  std::optional<PhaseTimer> all;  // HG_PHASE_SUBMIT, from the submission's start to mrlc_finish
+  MrlcFlow(hg_ctx* c_, const RlcCall& call_, size_t n_, bool members_, hipStream_t s_)
+      : c(c_), call(call_), n(n_), members(members_), s(s_), sub(c_, s_) {}
+  size_t ng() const { return rlc_groups(n, call.group); }
+};
+// grows the workspaces, starts the submission, draws the coefficients, forks hs and builds the G1 table there
+int mrlc_begin(MrlcFlow& f);
+// after the caller's H per check: r_i H_i and the join record
+int mrlc_hashed(MrlcFlow& f);
+// s waits for the join
+int mrlc_wait_hashed(MrlcFlow& f);
+// the combination over c->ws.checks and codes, the recheck of the failed groups' live members, the submission's end
+int mrlc_finish(MrlcFlow& f, int32_t* codes);

@@ -9,21 +9,11 @@
 // G2, and per group one Fp12 product, one final exponentiation and the verdict;
 // the live members of a group that fails, or that holds a key not proven in
 // G2, go through the exact two-pairing check (k_msgs_verify).
-#include <cstring>
-
 #include "bn256_brlc.h"
 #include "bn256_sigform.h"
 #include "hg_aggregate.h"
 
 namespace {
-
-struct BrlcCall {
-  const char* who;
-  const uint8_t* seed;       // 32 bytes, or
-  const uint64_t* d_coeffs;  // the probe's coefficients (device)
-  uint32_t group;
-  bool recheck;  // false: hg_debug_batch_rlc_groups stops after the group verdicts
-};
 
 // the batch on the device; off == nullptr: every check on the context's message
 struct BrlcBatch {
@@ -35,66 +25,22 @@ struct BrlcBatch {
   int32_t* codes;
 };
 
-RlcSeed seed_of(const uint8_t* seed) {
-  RlcSeed sd{};
-  if (seed) memcpy(sd.b, seed, 32);
-  return sd;
-}
-
 void clear_stats(hg_ctx* c) {
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   c->brlc_non_g2 = 0;
 }
 
-hipError_t brlc_ensure(hg_ctx* c, size_t n, size_t ng) {
-  Ws& ws = c->ws;
-  MsgWs& mw = c->msgs;
-  hipError_t e = hipSuccess;
-  auto grow = [&e](auto& buf, size_t count) {
-    if (e == hipSuccess) e = buf.ensure(count);
-  };
-  // the exact flows'
-  grow(ws.checks, n), grow(mw.k, 8 * n), grow(mw.hcodes, n), grow(mw.h, n);
-  // the combination's
-  grow(ws.pts1, n), grow(ws.rlc_r, n), grow(ws.rlc_jac, n);
-  grow(ws.rlc_glive, ng), grow(ws.rlc_gcodes, ng), grow(ws.rlc_gpts, ng), grow(ws.rlc_z, ng), grow(ws.rlc_hdr, 1);
-  grow(ws.sig_lines, fe12_ws_bytes((int)ng));
-  grow(mw.rk, 8 * n), grow(mw.rh, n), grow(mw.rchecks, n), grow(mw.f, n), grow(mw.carrier, ng), grow(mw.member, n);
-  return e;
-}
-
-// The failed groups' live members through the exact check (as hg_msgs_rlc.cpp):
-// gathered in index order with their unscaled H, verified as a batch of their
-// own, the codes scattered back.
-int brlc_recheck(hg_ctx* c, const BrlcBatch& b, uint32_t group, size_t m, hipStream_t s) {
-  Ws& ws = c->ws;
-  MsgWs& mw = c->msgs;
-  HG_CHECK(c, ws.rlc_bcount.ensure((b.n + 255) / 256));
-  HG_CHECK(c, ws.rlc_idx.ensure(m));
-  HG_CHECK(c, ws.rlc_ccodes.ensure(m));
-  HG_CHECK(c, mw.cchecks.ensure(m));
-  HG_CHECK(c, mw.ch.ensure(m));
-  launch_mrlc_gather(b.codes, ws.rlc_gcodes.p, (int)b.n, group, ws.checks.p, mw.h.p, ws.rlc_bcount.p, ws.rlc_idx.p,
-                     mw.cchecks.p, mw.ch.p, ws.rlc_ccodes.p, s);
-  launch_verify_msgs(mw.cchecks.p, (int)m, c->d_lines.p, mw.ch.p, ws.rlc_ccodes.p, s);
-  launch_rlc_scatter(ws.rlc_idx.p, ws.rlc_ccodes.p, (int)m, b.codes, s);
-  return HG_OK;
-}
-
-// One batch (n <= kSig12MaxN) on stream s with the context's workspaces.
-//   s:    coefficients, decode (cf: the subgroup check) -> wait -> merge -> G1 sums, scaled records,
-//         k_brlc_miller, k_mrlc_product, FE, verdicts, k_brlc_members (-> recheck)
-//   side: wait -> H per check (hashed, or the context's), k_mrlc_scalars, k_hash_points (r H) -> join
-int brlc_device_locked(hg_ctx* c, const BrlcBatch& b, const BrlcCall& call, hipStream_t s) {
+// One batch (n <= kSig12MaxN) on stream s with the context's workspaces (the
+// streams: MrlcFlow, hg_aggregate.h), the G2 membership of every key out of its
+// Miller loop.
+int brlc_device_locked(hg_ctx* c, const BrlcBatch& b, const RlcCall& call, hipStream_t s) {
   const bool one = b.off == nullptr;
   if (one && !c->cur.has_msg) {
     c->err = "hg_set_message was not called";
     return HG_ERR_ARG;
   }
-  const size_t n = b.n, ng = (n + call.group - 1) / call.group;
-  Ws& ws = c->ws;
+  const size_t n = b.n;
   MsgWs& mw = c->msgs;
-  const bool beside = c->pol.overlap;
   // hashedMessage's scalar of the context's message (hg_api.cpp set_message_locked)
   BrlcScalar k1{};
   bool hash_eof = false;
@@ -103,87 +49,32 @@ int brlc_device_locked(hg_ctx* c, const BrlcBatch& b, const BrlcCall& call, hipS
     sha256(c->cur.msg.data(), c->cur.msg.size(), d);
     hash_eof = !hash_scalar(d, k1.w);
   }
-  HG_CHECK(c, brlc_ensure(c, n, ng));
-  if (beside) HG_CHECK(c, ensure_side(ws));
-  Submission sub(c, s);
-  HG_CHECK(c, sub.start());
-  PhaseTimer all(c, HG_PHASE_SUBMIT, s);
-  launch_rlc_prep(seed_of(call.seed), call.d_coeffs, (int)n, (int)ng, ws.rlc_r.p, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
-  const hipStream_t hs = beside ? ws.side.h : s;
-  if (beside) {
-    HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
-    HG_CHECK(c, hipStreamWaitEvent(hs, ws.ev_fork, 0));
+  MrlcFlow f(c, call, n, true, s);
+  int rc = mrlc_begin(f);
+  if (rc) return rc;
+  // H_i: the context's for every check, or every check's own message hashed
+  if (one)
+    launch_brlc_one_message(k1, c->cur.d_h.p, hash_eof ? HG_ERR_HASH_EOF : HG_OK, (int)n, mw.k.p, mw.hcodes.p, mw.h.p,
+                            f.hs);
+  else {
+    launch_hash_scalars(b.pool, b.pool_len, b.off, b.len, (int)n, mw.k.p, mw.hcodes.p, f.hs);
+    launch_hash_points(mw.k.p, mw.hcodes.p, (int)n, mw.g1_tab.p, mw.h.p, f.hs);
   }
-  int rc = ensure_g1_table(c, hs);
-  if (rc == HG_OK) {
-    // H_i for the recheck and r_i H_i for the combination
-    if (one)
-      launch_brlc_one_message(k1, c->cur.d_h.p, hash_eof ? HG_ERR_HASH_EOF : HG_OK, (int)n, mw.k.p, mw.hcodes.p, mw.h.p,
-                              hs);
-    else {
-      launch_hash_scalars(b.pool, b.pool_len, b.off, b.len, (int)n, mw.k.p, mw.hcodes.p, hs);
-      launch_hash_points(mw.k.p, mw.hcodes.p, (int)n, mw.g1_tab.p, mw.h.p, hs);
-    }
-    launch_mrlc_scalars(mw.k.p, mw.hcodes.p, ws.rlc_r.p, (int)n, mw.rk.p, hs);
-    launch_hash_points(mw.rk.p, mw.hcodes.p, (int)n, mw.g1_tab.p, mw.rh.p, hs);
-    rc = check_launch(c);
-  }
-  if (beside) HG_CHECK(c, hipEventRecord(ws.ev_join, hs));
-  if (rc) {
-    if (beside) (void)hipStreamWaitEvent(s, ws.ev_join, 0);  // the submission's end covers the side stream
-    return rc;
-  }
+  rc = mrlc_hashed(f);
+  if (rc) return rc;
   // precedence: unmarshal of pk, of sig > hashedMessage's EOF > verdict
-  launch_decode_checks(b.pks, b.sigs, (int)n, c->flavor, ws.checks.p, b.codes, s);
-  if (beside) HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
+  launch_decode_checks(b.pks, b.sigs, (int)n, c->flavor, c->ws.checks.p, b.codes, s);
+  rc = mrlc_wait_hashed(f);
+  if (rc) return rc;
   launch_merge_hash_codes(mw.hcodes.p, (int)n, b.codes, s);
-  PhaseTimer t(c, HG_PHASE_VERIFY, s);
-  // sum r_i sig_i per group over the live members
-  launch_mrlc_sigs(ws.checks.p, (int)n, ws.pts1.p, s);
-  launch_rlc_g1_mul(ws.pts1.p, b.codes, ws.rlc_r.p, (int)n, ws.rlc_jac.p, s);
-  launch_rlc_g1_sum(ws.rlc_jac.p, b.codes, (int)n, call.group, (int)ng, ws.rlc_gpts.p, ws.rlc_glive.p, s);
-  launch_mrlc_checks(ws.checks.p, b.codes, ws.rlc_gpts.p, (int)n, call.group, (int)ng, mw.carrier.p, mw.rchecks.p, s);
-  launch_brlc_miller(mw.rchecks.p, (int)n, c->d_lines.p, mw.rh.p, 1, mw.f.p, mw.member.p, s);
-  launch_mrlc_product(mw.f.p, b.codes, (int)n, call.group, (int)ng, ws.rlc_z.p, s);
-  if (!launch_fe12(ws.rlc_z.p, (int)ng, ws.sig_lines.p, s)) {
-    c->err = std::string(call.who) + ": too many groups for the final exponentiation";
-    return HG_ERR_ARG;
-  }
-  launch_fe_verdicts(ws.rlc_z.p, (int)ng, ws.rlc_gcodes.p, s);
-  // a group is accepted only if every live key of it is proven in G2
-  launch_brlc_members(b.codes, mw.member.p, (int)n, call.group, (int)ng, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
-  launch_rlc_count(ws.rlc_gcodes.p, ws.rlc_glive.p, (int)ng, ws.rlc_hdr.p, s);
-  rc = check_launch(c);
-  if (rc) return rc;
-  if (call.recheck) {
-    // the one read-back: how many checks the failed groups hold sizes their launch
-    RlcHdr h{};
-    HG_CHECK(c, hipMemcpyAsync(&h, ws.rlc_hdr.p, sizeof h, hipMemcpyDeviceToHost, s));
-    HG_CHECK(c, hipStreamSynchronize(s));
-    c->rlc_stats[0] = h.groups;
-    c->rlc_stats[1] = h.groups_failed;
-    c->rlc_stats[2] = h.failed_members;
-    c->brlc_non_g2 = h.pad;
-    if (h.failed_members > n) {
-      c->err = std::string(call.who) + ": inconsistent failed-member count";
-      return HG_ERR_DEVICE;
-    }
-    if (h.failed_members) {
-      rc = brlc_recheck(c, b, call.group, h.failed_members, s);
-      if (rc) return rc;
-    }
-  }
-  t.stop();
-  all.stop();
-  rc = check_launch(c);
-  if (rc) return rc;
-  HG_CHECK(c, sub.finish());
-  return HG_OK;
+  rc = mrlc_finish(f, b.codes);
+  c->brlc_non_g2 = f.hdr.non_g2;  // zero, as the entry point left it, unless the read-back ran
+  return rc;
 }
 
 // host pointers in, through the context's staging buffers (as hg_verify_batch, hg_verify_batch_msgs)
 int brlc_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* off, const uint32_t* len,
-                     const uint8_t* pks, const uint8_t* sigs, size_t n, const uint64_t* coeffs, const BrlcCall& call0,
+                     const uint8_t* pks, const uint8_t* sigs, size_t n, const uint64_t* coeffs, const RlcCall& call0,
                      int32_t* codes, int32_t* group_codes, uint32_t* group_live) {
   if (off) {
     int rc = check_ranges(c, call0.who, pool_len, off, len, n);
@@ -204,7 +95,7 @@ int brlc_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint
   HG_CHECK(c, hipMemcpyAsync(c->bytes_a.p, pks, n * 128, hipMemcpyHostToDevice, s));
   HG_CHECK(c, hipMemcpyAsync(c->bytes_b.p, sigs, n * 64, hipMemcpyHostToDevice, s));
   if (coeffs) HG_CHECK(c, hipMemcpyAsync(c->words.p, coeffs, n * 8, hipMemcpyHostToDevice, s));
-  BrlcCall call = call0;
+  RlcCall call = call0;
   call.d_coeffs = coeffs ? c->words.p : nullptr;
   const BrlcBatch b{off ? c->msgs.pool.p : nullptr, pool_len, off ? c->msgs.off.p : nullptr,
                     off ? c->msgs.len.p : nullptr, c->bytes_a.p, c->bytes_b.p, n, c->ws.codes_c.p};
@@ -212,16 +103,14 @@ int brlc_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint
   if (rc) return rc;
   HG_CHECK(c, hipMemcpyAsync(codes, b.codes, n * 4, hipMemcpyDeviceToHost, s));
   if (group_codes) {
-    const size_t ng = (n + call.group - 1) / call.group;
-    HG_CHECK(c, hipMemcpyAsync(group_codes, c->ws.rlc_gcodes.p, ng * 4, hipMemcpyDeviceToHost, s));
-    HG_CHECK(c, hipMemcpyAsync(group_live, c->ws.rlc_glive.p, ng * 4, hipMemcpyDeviceToHost, s));
+    rc = rlc_copy_groups(c, rlc_groups(n, call.group), group_codes, group_live, s);
+    if (rc) return rc;
   }
   HG_CHECK(c, sub.finish());
   HG_CHECK(c, hipStreamSynchronize(s));
   return HG_OK;
 }
 
-bool group_ok(uint32_t group) { return group >= 1 && group <= kRlcMaxGroup; }
 // above this the combination's kernels cannot index the batch: the exact call runs
 bool too_large(size_t n) { return n > (size_t)kSig12MaxN; }
 
@@ -231,21 +120,22 @@ extern "C" {
 
 int hg_verify_batch_rlc(hg_ctx* c, const uint8_t* pks, const uint8_t* sigs, size_t n, const uint8_t seed[32],
                         uint32_t group, int32_t* codes) {
-  if (!c || !seed || !group_ok(group) || (n && (!pks || !sigs || !codes)) || n > (size_t)INT32_MAX) return HG_ERR_ARG;
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!pks || !sigs || !codes)) || n > (size_t)INT32_MAX)
+    return HG_ERR_ARG;
   {
     std::lock_guard<std::mutex> g(c->mu);
     clear_stats(c);
     if (n == 0) return HG_OK;
     if (!too_large(n))
       return brlc_host_locked(c, nullptr, 0, nullptr, nullptr, pks, sigs, n, nullptr,
-                              BrlcCall{"hg_verify_batch_rlc", seed, nullptr, group, true}, codes, nullptr, nullptr);
+                              RlcCall{"hg_verify_batch_rlc", seed, nullptr, group, true}, codes, nullptr, nullptr);
   }
   return hg_verify_batch(c, pks, sigs, n, codes);
 }
 
 int hg_verify_batch_rlc_device(hg_ctx* c, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n,
                                const uint8_t seed[32], uint32_t group, int32_t* d_codes, void* stream) {
-  if (!c || !seed || !group_ok(group) || (n && (!d_pks || !d_sigs || !d_codes)) || n > (size_t)INT32_MAX)
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!d_pks || !d_sigs || !d_codes)) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   {
     std::lock_guard<std::mutex> g(c->mu);
@@ -255,7 +145,7 @@ int hg_verify_batch_rlc_device(hg_ctx* c, const uint8_t* d_pks, const uint8_t* d
       HG_CHECK(c, hipSetDevice(c->device));
       hipStream_t s = stream ? (hipStream_t)stream : c->stream;
       return brlc_device_locked(c, BrlcBatch{nullptr, 0, nullptr, nullptr, d_pks, d_sigs, n, d_codes},
-                                BrlcCall{"hg_verify_batch_rlc_device", seed, nullptr, group, true}, s);
+                                RlcCall{"hg_verify_batch_rlc_device", seed, nullptr, group, true}, s);
     }
   }
   return hg_verify_batch_device(c, d_pks, d_sigs, n, d_codes, stream);
@@ -264,7 +154,7 @@ int hg_verify_batch_rlc_device(hg_ctx* c, const uint8_t* d_pks, const uint8_t* d
 int hg_verify_batch_msgs_rlc(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
                              const uint32_t* msg_len, const uint8_t* pks, const uint8_t* sigs, size_t n,
                              const uint8_t seed[32], uint32_t group, int32_t* codes) {
-  if (!c || !seed || !group_ok(group) || (n && (!msg_off || !msg_len || !pks || !sigs || !codes)) ||
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!msg_off || !msg_len || !pks || !sigs || !codes)) ||
       (!pool && pool_len) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   {
@@ -273,7 +163,7 @@ int hg_verify_batch_msgs_rlc(hg_ctx* c, const uint8_t* pool, size_t pool_len, co
     if (n == 0) return HG_OK;
     if (!too_large(n))
       return brlc_host_locked(c, pool, pool_len, msg_off, msg_len, pks, sigs, n, nullptr,
-                              BrlcCall{"hg_verify_batch_msgs_rlc", seed, nullptr, group, true}, codes, nullptr,
+                              RlcCall{"hg_verify_batch_msgs_rlc", seed, nullptr, group, true}, codes, nullptr,
                               nullptr);
   }
   return hg_verify_batch_msgs(c, pool, pool_len, msg_off, msg_len, pks, sigs, n, codes);
@@ -282,7 +172,7 @@ int hg_verify_batch_msgs_rlc(hg_ctx* c, const uint8_t* pool, size_t pool_len, co
 int hg_verify_batch_msgs_rlc_device(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
                                     const uint32_t* d_msg_len, const uint8_t* d_pks, const uint8_t* d_sigs, size_t n,
                                     const uint8_t seed[32], uint32_t group, int32_t* d_codes, void* stream) {
-  if (!c || !seed || !group_ok(group) || (n && (!d_msg_off || !d_msg_len || !d_pks || !d_sigs || !d_codes)) ||
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!d_msg_off || !d_msg_len || !d_pks || !d_sigs || !d_codes)) ||
       (!d_pool && pool_len) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   {
@@ -293,7 +183,7 @@ int hg_verify_batch_msgs_rlc_device(hg_ctx* c, const uint8_t* d_pool, size_t poo
       HG_CHECK(c, hipSetDevice(c->device));
       hipStream_t s = stream ? (hipStream_t)stream : c->stream;
       return brlc_device_locked(c, BrlcBatch{d_pool, pool_len, d_msg_off, d_msg_len, d_pks, d_sigs, n, d_codes},
-                                BrlcCall{"hg_verify_batch_msgs_rlc_device", seed, nullptr, group, true}, s);
+                                RlcCall{"hg_verify_batch_msgs_rlc_device", seed, nullptr, group, true}, s);
     }
   }
   return hg_verify_batch_msgs_device(c, d_pool, pool_len, d_msg_off, d_msg_len, d_pks, d_sigs, n, d_codes, stream);
@@ -345,14 +235,14 @@ int hg_debug_batch_rlc_groups(hg_ctx* c, const uint8_t* pool, size_t pool_len, c
                               const uint32_t* msg_len, const uint8_t* pks, const uint8_t* sigs, size_t n,
                               const uint64_t* coeffs, uint32_t group, int32_t* codes, int32_t* group_codes,
                               uint32_t* group_live) {
-  if (!c || !group_ok(group) || (n && (!pks || !sigs || !coeffs || !codes || !group_codes || !group_live)) ||
+  if (!c || !rlc_group_ok(group) || (n && (!pks || !sigs || !coeffs || !codes || !group_codes || !group_live)) ||
       (msg_off == nullptr) != (msg_len == nullptr) || (!pool && pool_len) || too_large(n))
     return HG_ERR_ARG;
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   clear_stats(c);
   return brlc_host_locked(c, pool, pool_len, msg_off, msg_len, pks, sigs, n, coeffs,
-                          BrlcCall{"hg_debug_batch_rlc_groups", nullptr, nullptr, group, false}, codes, group_codes,
+                          RlcCall{"hg_debug_batch_rlc_groups", nullptr, nullptr, group, false}, codes, group_codes,
                           group_live);
 }
 

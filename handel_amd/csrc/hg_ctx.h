@@ -4,11 +4,10 @@
 // (context, message, registry, single checks), hg_gttables.cpp (GT tables),
 // hg_aggregate.cpp (aggregate verification), hg_lanes.cpp (service lanes),
 // hg_rlc.cpp (its random-linear-combination form), hg_intake.cpp (packets,
-// stores), hg_msgs.cpp (checks on their own messages) and hg_msgs_rlc.cpp
-// (their random-linear-combination form) and hg_batch_rlc.cpp (independent
-// checks in that form) include it. Every
-// device resource below is held by an owner of hg_dev.h, so deleting a
-// context, a lane or a store set frees what it holds.
+// stores), hg_msgs.cpp (checks on their own messages), hg_msgs_rlc.cpp (their
+// random-linear-combination form) and hg_batch_rlc.cpp (independent checks in
+// that form) include it. Every device resource below is held by an owner of
+// hg_dev.h, so deleting a context, a lane or a store set frees what it holds.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,10 +95,11 @@ struct MsgWs {
   DevBuf<PointG1> h;         // H per check
   DevBuf<uint8_t> pool;      // the host variants' staging: messages,
   DevBuf<uint32_t> off, len; // their offsets and lengths
-  // hg_verify_aggregate_msgs_rlc* (hg_msgs_rlc.cpp, bn256_msgsrlc.hip): per
-  // request r_i k_i mod Order, r_i H_i, the scaled check record and the Miller
-  // value; per group its first live member; and, grown only when a group
-  // fails, the recheck's compact check records and their H
+  // the combined flow of hg_verify_aggregate_msgs_rlc*, hg_verify_batch_rlc*
+  // and hg_verify_batch_msgs_rlc* (MrlcFlow, hg_msgs_rlc.cpp; bn256_msgsrlc.hip):
+  // per check r_i k_i mod Order, r_i H_i, the scaled check record and the
+  // Miller value; per group its first live member; and, grown only when a
+  // group fails, the recheck's compact check records and their H
   DevBuf<uint32_t> rk;
   DevBuf<PointG1> rh;
   DevBuf<CheckIn> rchecks;
@@ -107,8 +107,8 @@ struct MsgWs {
   DevBuf<uint32_t> carrier;
   DevBuf<CheckIn> cchecks;
   DevBuf<PointG1> ch;
-  // hg_verify_batch_rlc*, hg_verify_batch_msgs_rlc* (hg_batch_rlc.cpp): the
-  // G2 membership verdict of every check's key (bn256_batchrlc.hip)
+  // the G2 membership verdict of every check's key (bn256_batchrlc.hip), grown
+  // only by a flow that asks for it (hg_batch_rlc.cpp) and by hg_debug_g2_member
   DevBuf<uint32_t> member;
   size_t bytes() const {
     return g1_tab.bytes() + k.bytes() + hcodes.bytes() + h.bytes() + pool.bytes() + off.bytes() + len.bytes() +
@@ -188,7 +188,7 @@ struct hg_ctx {
   DevBuf<hg_request> reqs;
   DevBuf<hg_packet> pkts;  // hg_parse_packets staging
   DevBuf<uint64_t> words;
-  MsgWs msgs;  // hg_verify_batch_msgs*, hg_hash_messages
+  MsgWs msgs;  // hg_verify_batch_msgs*, hg_verify_aggregate_msgs*, hg_hash_messages and the combined forms of both
   // -1: the volume policy; 0..2: every aggregate submission at that level
   // (hg_set_aggregate_level; HG_GT_LEVEL / HG_AGG_PATH give the default)
   int pinned_level = -1;
@@ -211,8 +211,8 @@ struct hg_ctx {
   // the context's own aggregate submissions: padded, the two-wave form up to
   // kSigW2MaxN; overlap: hg_set_fold_overlap (HG_GT_OVERLAP=0 gives new contexts false)
   SigPolicy pol;
-  // hg_rlc_stats: the last hg_verify_aggregate_rlc* or hg_verify_*_msgs_rlc* call's groups checked, groups
-  // failed, checks re-verified
+  // hg_rlc_stats, hg_batch_rlc_stats: the last combined call's (hg_verify_aggregate_rlc*, hg_verify_*_msgs_rlc*,
+  // hg_verify_batch_rlc*) groups checked, groups failed, checks re-verified; rlc_read_stats (hg_rlc.cpp) sets them
   uint64_t rlc_stats[3] = {0, 0, 0};
   // hg_batch_rlc_stats: the last hg_verify_batch*_rlc* call's live checks whose key was not proven in G2
   uint64_t brlc_non_g2 = 0;

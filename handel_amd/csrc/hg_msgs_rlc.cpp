@@ -10,18 +10,137 @@
 // runs the exact call as it stands.
 #include <cstring>
 
+#include "bn256_brlc.h"
 #include "bn256_sigform.h"
 #include "hg_aggregate.h"
 
+// ---------------------------------------------------------------- the combined flow (MrlcFlow, hg_aggregate.h)
+// of checks that carry a message each: this file's requests and hg_batch_rlc.cpp's independent checks
 namespace {
 
-struct MrlcCall {
-  const char* who;
-  const uint8_t* seed;       // 32 bytes, or
-  const uint64_t* d_coeffs;  // the probe's coefficients (device)
-  uint32_t group;
-  bool recheck;  // false: hg_debug_msgs_rlc_groups stops after the group verdicts
-};
+hipError_t mrlc_ensure(hg_ctx* c, size_t n, size_t ng, bool members) {
+  Ws& ws = c->ws;
+  MsgWs& mw = c->msgs;
+  hipError_t e = hipSuccess;
+  auto grow = [&e](auto& buf, size_t count) {
+    if (e == hipSuccess) e = buf.ensure(count);
+  };
+  // the exact flows'
+  grow(ws.checks, n), grow(mw.k, 8 * n), grow(mw.hcodes, n), grow(mw.h, n);
+  // the combination's
+  grow(ws.pts1, n), grow(ws.rlc_r, n), grow(ws.rlc_jac, n);
+  grow(ws.rlc_glive, ng), grow(ws.rlc_gcodes, ng), grow(ws.rlc_gpts, ng), grow(ws.rlc_z, ng), grow(ws.rlc_hdr, 1);
+  grow(ws.sig_lines, fe12_ws_bytes((int)ng));
+  grow(mw.rk, 8 * n), grow(mw.rh, n), grow(mw.rchecks, n), grow(mw.f, n), grow(mw.carrier, ng);
+  if (members) grow(mw.member, n);
+  return e;
+}
+
+// The failed groups' live members through the exact check: gathered in index
+// order with their unscaled H, verified as a batch of their own, the codes
+// scattered back.
+int mrlc_recheck(hg_ctx* c, int32_t* codes, size_t n, uint32_t group, size_t m, hipStream_t s) {
+  Ws& ws = c->ws;
+  MsgWs& mw = c->msgs;
+  HG_CHECK(c, ws.rlc_bcount.ensure((n + 255) / 256));
+  HG_CHECK(c, ws.rlc_idx.ensure(m));
+  HG_CHECK(c, ws.rlc_ccodes.ensure(m));
+  HG_CHECK(c, mw.cchecks.ensure(m));
+  HG_CHECK(c, mw.ch.ensure(m));
+  launch_mrlc_gather(codes, ws.rlc_gcodes.p, (int)n, group, ws.checks.p, mw.h.p, ws.rlc_bcount.p, ws.rlc_idx.p,
+                     mw.cchecks.p, mw.ch.p, ws.rlc_ccodes.p, s);
+  launch_verify_msgs(mw.cchecks.p, (int)m, c->d_lines.p, mw.ch.p, ws.rlc_ccodes.p, s);
+  launch_rlc_scatter(ws.rlc_idx.p, ws.rlc_ccodes.p, (int)m, codes, s);
+  return HG_OK;
+}
+
+// The hash stream's end: its join record; after an error the wait for it as
+// well, so that the submission's end covers the side stream.
+int mrlc_join(MrlcFlow& f, int rc) {
+  hg_ctx* c = f.c;
+  if (f.hs == f.s) return rc;
+  HG_CHECK(c, hipEventRecord(c->ws.ev_join, f.hs));
+  if (rc) (void)hipStreamWaitEvent(f.s, c->ws.ev_join, 0);
+  return rc;
+}
+
+}  // namespace
+
+int mrlc_begin(MrlcFlow& f) {
+  hg_ctx* c = f.c;
+  Ws& ws = c->ws;
+  const bool beside = c->pol.overlap;
+  HG_CHECK(c, mrlc_ensure(c, f.n, f.ng(), f.members));
+  if (beside) HG_CHECK(c, ensure_side(ws));
+  HG_CHECK(c, f.sub.start());
+  f.all.emplace(c, HG_PHASE_SUBMIT, f.s);
+  launch_rlc_prep(rlc_seed_of(f.call.seed), f.call.d_coeffs, (int)f.n, (int)f.ng(), ws.rlc_r.p, ws.rlc_gcodes.p,
+                  ws.rlc_hdr.p, f.s);
+  f.hs = beside ? ws.side.h : f.s;
+  if (beside) {
+    HG_CHECK(c, hipEventRecord(ws.ev_fork, f.s));
+    HG_CHECK(c, hipStreamWaitEvent(f.hs, ws.ev_fork, 0));
+  }
+  const int rc = ensure_g1_table(c, f.hs);
+  return rc ? mrlc_join(f, rc) : HG_OK;
+}
+
+int mrlc_hashed(MrlcFlow& f) {
+  hg_ctx* c = f.c;
+  MsgWs& mw = c->msgs;
+  // H_i (the caller's) for the recheck and r_i H_i for the combination: two walks
+  // of the fixed-base table, no G1 chain and no inversion more than that
+  launch_mrlc_scalars(mw.k.p, mw.hcodes.p, c->ws.rlc_r.p, (int)f.n, mw.rk.p, f.hs);
+  launch_hash_points(mw.rk.p, mw.hcodes.p, (int)f.n, mw.g1_tab.p, mw.rh.p, f.hs);
+  return mrlc_join(f, check_launch(c));
+}
+
+int mrlc_wait_hashed(MrlcFlow& f) {
+  if (f.hs != f.s) HG_CHECK(f.c, hipStreamWaitEvent(f.s, f.c->ws.ev_join, 0));
+  return HG_OK;
+}
+
+int mrlc_finish(MrlcFlow& f, int32_t* codes) {
+  hg_ctx* c = f.c;
+  Ws& ws = c->ws;
+  MsgWs& mw = c->msgs;
+  const hipStream_t s = f.s;
+  const int n = (int)f.n, ng = (int)f.ng();
+  const uint32_t group = f.call.group;
+  PhaseTimer t(c, HG_PHASE_VERIFY, s);
+  // sum r_i sig_i per group over the live members
+  launch_mrlc_sigs(ws.checks.p, n, ws.pts1.p, s);
+  launch_rlc_g1_mul(ws.pts1.p, codes, ws.rlc_r.p, n, ws.rlc_jac.p, s);
+  launch_rlc_g1_sum(ws.rlc_jac.p, codes, n, group, ng, ws.rlc_gpts.p, ws.rlc_glive.p, s);
+  launch_mrlc_checks(ws.checks.p, codes, ws.rlc_gpts.p, n, group, ng, mw.carrier.p, mw.rchecks.p, s);
+  if (f.members) launch_brlc_miller(mw.rchecks.p, n, c->d_lines.p, mw.rh.p, 1, mw.f.p, mw.member.p, s);
+  else launch_mrlc_miller(mw.rchecks.p, n, c->d_lines.p, mw.rh.p, mw.f.p, s);
+  launch_mrlc_product(mw.f.p, codes, n, group, ng, ws.rlc_z.p, s);
+  if (!launch_fe12(ws.rlc_z.p, ng, ws.sig_lines.p, s)) {
+    c->err = std::string(f.call.who) + ": too many groups for the final exponentiation";
+    return HG_ERR_ARG;
+  }
+  launch_fe_verdicts(ws.rlc_z.p, ng, ws.rlc_gcodes.p, s);
+  // a group is accepted only if every live key of it is proven in G2
+  if (f.members) launch_brlc_members(codes, mw.member.p, n, group, ng, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
+  launch_rlc_count(ws.rlc_gcodes.p, ws.rlc_glive.p, ng, ws.rlc_hdr.p, s);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  if (f.call.recheck) {
+    rc = rlc_read_stats(c, f.call, f.n, s, &f.hdr);
+    if (rc == HG_OK && f.hdr.failed_members) rc = mrlc_recheck(c, codes, f.n, group, f.hdr.failed_members, s);
+    if (rc) return rc;
+  }
+  t.stop();
+  f.all->stop();
+  rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, f.sub.finish());
+  return HG_OK;
+}
+
+// ---------------------------------------------------------------- hg_verify_aggregate_msgs_rlc* and the probes
+namespace {
 
 // the batch's messages and requests on the device
 struct MsgBatch {
@@ -35,61 +154,16 @@ struct MsgBatch {
   int32_t* codes;
 };
 
-RlcSeed seed_of(const uint8_t* seed) {
-  RlcSeed sd{};
-  if (seed) memcpy(sd.b, seed, 32);
-  return sd;
-}
-
-hipError_t mrlc_ensure(hg_ctx* c, size_t n, size_t ng) {
-  Ws& ws = c->ws;
-  MsgWs& mw = c->msgs;
-  hipError_t e = hipSuccess;
-  auto grow = [&e](auto& buf, size_t count) {
-    if (e == hipSuccess) e = buf.ensure(count);
-  };
-  // the exact flow's
-  grow(ws.checks, n), grow(ws.order, n), grow(ws.agg_ws, n * agg_partial_bytes() + agg_fixed_bytes());
-  grow(ws.codes_c, n), grow(mw.k, 8 * n), grow(mw.hcodes, n), grow(mw.h, n);
-  // the combination's
-  grow(ws.pts1, n), grow(ws.rlc_r, n), grow(ws.rlc_jac, n);
-  grow(ws.rlc_glive, ng), grow(ws.rlc_gcodes, ng), grow(ws.rlc_gpts, ng), grow(ws.rlc_z, ng), grow(ws.rlc_hdr, 1);
-  grow(ws.sig_lines, fe12_ws_bytes((int)ng));
-  grow(mw.rk, 8 * n), grow(mw.rh, n), grow(mw.rchecks, n), grow(mw.f, n), grow(mw.carrier, ng);
-  return e;
-}
-
-// The failed groups' live members through the exact check: gathered in index
-// order with their unscaled H, verified as a batch of their own, the codes
-// scattered back.
-int mrlc_recheck(hg_ctx* c, const MsgBatch& b, uint32_t group, size_t m, hipStream_t s) {
-  Ws& ws = c->ws;
-  MsgWs& mw = c->msgs;
-  HG_CHECK(c, ws.rlc_bcount.ensure((b.n + 255) / 256));
-  HG_CHECK(c, ws.rlc_idx.ensure(m));
-  HG_CHECK(c, ws.rlc_ccodes.ensure(m));
-  HG_CHECK(c, mw.cchecks.ensure(m));
-  HG_CHECK(c, mw.ch.ensure(m));
-  launch_mrlc_gather(b.codes, ws.rlc_gcodes.p, (int)b.n, group, ws.checks.p, mw.h.p, ws.rlc_bcount.p, ws.rlc_idx.p,
-                     mw.cchecks.p, mw.ch.p, ws.rlc_ccodes.p, s);
-  launch_verify_msgs(mw.cchecks.p, (int)m, c->d_lines.p, mw.ch.p, ws.rlc_ccodes.p, s);
-  launch_rlc_scatter(ws.rlc_idx.p, ws.rlc_ccodes.p, (int)m, b.codes, s);
-  return HG_OK;
-}
-
-// One batch on stream s with the context's workspaces. *ran: the combination
-// ran (false: the exact call did).
-//   s:    coefficients -> level codes, G2 fold ............ -> wait -> merge -> G1 sums, scaled records,
-//                                                             k_mrlc_miller, k_mrlc_product, FE, verdicts (-> recheck)
-//   side: wait -> k_hash_scalars, k_hash_points (H), k_mrlc_scalars, k_hash_points (r H) -> join
-int mrlc_device_locked(hg_ctx* c, const MsgBatch& b, const MrlcCall& call, bool* ran, hipStream_t s) {
+// One batch on stream s with the context's workspaces (the streams: MrlcFlow,
+// hg_aggregate.h). *ran: the combination ran (false: the exact call did).
+int mrlc_device_locked(hg_ctx* c, const MsgBatch& b, const RlcCall& call, bool* ran, hipStream_t s) {
   *ran = false;
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (c->nreg == 0) {
     c->err = std::string(call.who) + ": needs a registry";
     return HG_ERR_ARG;
   }
-  const size_t n = b.n, ng = (n + call.group - 1) / call.group;
+  const size_t n = b.n;
   // Every D_i = e(H_i, agg_i) e(-sig_i, G2Base) must lie in the order-n
   // subgroup: aggregates of a registry proven in G2 do (G1 has cofactor 1).
   int rc = resolve_subgroup(c);
@@ -104,85 +178,34 @@ int mrlc_device_locked(hg_ctx* c, const MsgBatch& b, const MrlcCall& call, bool*
   }
   Ws& ws = c->ws;
   MsgWs& mw = c->msgs;
-  const bool beside = c->pol.overlap;
-  HG_CHECK(c, mrlc_ensure(c, n, ng));
-  if (beside) HG_CHECK(c, ensure_side(ws));
-  Submission sub(c, s);
-  HG_CHECK(c, sub.start());
-  PhaseTimer all(c, HG_PHASE_SUBMIT, s);
-  launch_rlc_prep(seed_of(call.seed), call.d_coeffs, (int)n, (int)ng, ws.rlc_r.p, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
-  const hipStream_t hs = beside ? ws.side.h : s;
-  if (beside) {
-    HG_CHECK(c, hipEventRecord(ws.ev_fork, s));
-    HG_CHECK(c, hipStreamWaitEvent(hs, ws.ev_fork, 0));
-  }
-  rc = ensure_g1_table(c, hs);
-  if (rc == HG_OK) {
-    // H_i for the recheck and r_i H_i for the combination: two walks of the
-    // fixed-base table, no G1 chain and no inversion more than that
-    launch_hash_scalars(b.pool, b.pool_len, b.off, b.len, (int)n, mw.k.p, mw.hcodes.p, hs);
-    launch_hash_points(mw.k.p, mw.hcodes.p, (int)n, mw.g1_tab.p, mw.h.p, hs);
-    launch_mrlc_scalars(mw.k.p, mw.hcodes.p, ws.rlc_r.p, (int)n, mw.rk.p, hs);
-    launch_hash_points(mw.rk.p, mw.hcodes.p, (int)n, mw.g1_tab.p, mw.rh.p, hs);
-    rc = check_launch(c);
-  }
-  if (beside) HG_CHECK(c, hipEventRecord(ws.ev_join, hs));
-  if (rc) {
-    if (beside) (void)hipStreamWaitEvent(s, ws.ev_join, 0);  // the submission's end covers the side stream
-    return rc;
-  }
+  // the exact flow's fold
+  HG_CHECK(c, ws.order.ensure(n));
+  HG_CHECK(c, ws.agg_ws.ensure(n * agg_partial_bytes() + agg_fixed_bytes()));
+  HG_CHECK(c, ws.codes_c.ensure(n));
+  MrlcFlow f(c, call, n, false, s);
+  rc = mrlc_begin(f);
+  if (rc) return rc;
+  // H_i: every request's own message hashed
+  launch_hash_scalars(b.pool, b.pool_len, b.off, b.len, (int)n, mw.k.p, mw.hcodes.p, f.hs);
+  launch_hash_points(mw.k.p, mw.hcodes.p, (int)n, mw.g1_tab.p, mw.h.p, f.hs);
+  rc = mrlc_hashed(f);
+  if (rc) return rc;
   launch_aggmsgs_levels(b.reqs, (int)n, (uint32_t)c->nreg, ws.codes_c.p, s);
   PhaseTimer fold(c, HG_PHASE_AGGREGATE, s);
   launch_aggregate(c->wsum.p, (int)c->nreg, c->blocks.p, c->block_base.data(), c->block_levels, b.reqs, (int)n, b.words,
                    ws.order.p, ws.agg_ws.p, ws.checks.p, ws.codes_c.p, s);
   fold.stop();
-  if (beside) HG_CHECK(c, hipStreamWaitEvent(s, ws.ev_join, 0));
+  rc = mrlc_wait_hashed(f);
+  if (rc) return rc;
   launch_aggmsgs_merge(b.sigs, (int)n, c->flavor, ws.codes_c.p, mw.hcodes.p, ws.checks.p, b.codes, s);
-  PhaseTimer t(c, HG_PHASE_VERIFY, s);
-  // sum r_i sig_i per group over the live members
-  launch_mrlc_sigs(ws.checks.p, (int)n, ws.pts1.p, s);
-  launch_rlc_g1_mul(ws.pts1.p, b.codes, ws.rlc_r.p, (int)n, ws.rlc_jac.p, s);
-  launch_rlc_g1_sum(ws.rlc_jac.p, b.codes, (int)n, call.group, (int)ng, ws.rlc_gpts.p, ws.rlc_glive.p, s);
-  launch_mrlc_checks(ws.checks.p, b.codes, ws.rlc_gpts.p, (int)n, call.group, (int)ng, mw.carrier.p, mw.rchecks.p, s);
-  launch_mrlc_miller(mw.rchecks.p, (int)n, c->d_lines.p, mw.rh.p, mw.f.p, s);
-  launch_mrlc_product(mw.f.p, b.codes, (int)n, call.group, (int)ng, ws.rlc_z.p, s);
-  if (!launch_fe12(ws.rlc_z.p, (int)ng, ws.sig_lines.p, s)) {
-    c->err = std::string(call.who) + ": too many groups for the final exponentiation";
-    return HG_ERR_ARG;
-  }
-  launch_fe_verdicts(ws.rlc_z.p, (int)ng, ws.rlc_gcodes.p, s);
-  launch_rlc_count(ws.rlc_gcodes.p, ws.rlc_glive.p, (int)ng, ws.rlc_hdr.p, s);
-  rc = check_launch(c);
-  if (rc) return rc;
-  *ran = true;
-  if (call.recheck) {
-    // the one read-back: how many requests the failed groups hold sizes their launch
-    RlcHdr h{};
-    HG_CHECK(c, hipMemcpyAsync(&h, ws.rlc_hdr.p, sizeof h, hipMemcpyDeviceToHost, s));
-    HG_CHECK(c, hipStreamSynchronize(s));
-    c->rlc_stats[0] = h.groups;
-    c->rlc_stats[1] = h.groups_failed;
-    c->rlc_stats[2] = h.failed_members;
-    if (h.failed_members > n) {
-      c->err = std::string(call.who) + ": inconsistent failed-member count";
-      return HG_ERR_DEVICE;
-    }
-    if (h.failed_members) {
-      rc = mrlc_recheck(c, b, call.group, h.failed_members, s);
-      if (rc) return rc;
-    }
-  }
-  t.stop();
-  all.stop();
-  rc = check_launch(c);
-  if (rc) return rc;
-  HG_CHECK(c, sub.finish());
-  return HG_OK;
+  rc = mrlc_finish(f, b.codes);
+  *ran = rc == HG_OK;
+  return rc;
 }
 
 // host pointers in, through the context's staging buffers (as hg_verify_aggregate_msgs)
 int mrlc_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* off, const uint32_t* len,
-                     const HostBatch& h, const uint64_t* coeffs, const MrlcCall& call0, int32_t* codes,
+                     const HostBatch& h, const uint64_t* coeffs, const RlcCall& call0, int32_t* codes,
                      int32_t* group_codes, uint32_t* group_live) {
   const size_t n = h.n;
   int rc = check_ranges(c, h.who, pool_len, off, len, n);
@@ -198,7 +221,7 @@ int mrlc_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint
   if (rc == HG_OK) rc = stage_messages(c, pool, pool_len, off, len, n);
   if (rc == HG_OK && coeffs) rc = st.put(c->bytes_a, coeffs, n * 8);
   if (rc) return rc;
-  MrlcCall call = call0;
+  RlcCall call = call0;
   call.d_coeffs = coeffs ? reinterpret_cast<const uint64_t*>(c->bytes_a.p) : nullptr;
   const AggBatch ab = st.batch(h);
   const MsgBatch b{c->msgs.pool.p, pool_len, c->msgs.off.p, c->msgs.len.p, ab.reqs, n, ab.words, ab.sigs, ab.codes};
@@ -206,14 +229,11 @@ int mrlc_host_locked(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint
   rc = mrlc_device_locked(c, b, call, &ran, c->stream);
   if (rc) return rc;
   if (group_codes && ran) {
-    const size_t ng = (n + call.group - 1) / call.group;
-    HG_CHECK(c, hipMemcpyAsync(group_codes, c->ws.rlc_gcodes.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
-    HG_CHECK(c, hipMemcpyAsync(group_live, c->ws.rlc_glive.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
+    rc = rlc_copy_groups(c, rlc_groups(n, call.group), group_codes, group_live, c->stream);
+    if (rc) return rc;
   }
   return st.close(h, b.codes, codes, nullptr);
 }
-
-bool group_ok(uint32_t group) { return group >= 1 && group <= kRlcMaxGroup; }
 
 }  // namespace
 
@@ -223,51 +243,51 @@ int hg_verify_aggregate_msgs_rlc(hg_ctx* c, const uint8_t* pool, size_t pool_len
                                  const uint32_t* msg_len, const hg_request* reqs, size_t n, const uint64_t* words,
                                  size_t nwords, const uint8_t* sigs, const uint8_t seed[32], uint32_t group,
                                  int32_t* codes) {
-  if (!c || !seed || !group_ok(group) || (n && (!msg_off || !msg_len || !reqs || !sigs || !codes)) ||
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!msg_off || !msg_len || !reqs || !sigs || !codes)) ||
       (!pool && pool_len) || (!words && nwords) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (n == 0) return HG_OK;
   return mrlc_host_locked(c, pool, pool_len, msg_off, msg_len,
                           HostBatch{"hg_verify_aggregate_msgs_rlc", reqs, n, words, nwords, sigs}, nullptr,
-                          MrlcCall{"hg_verify_aggregate_msgs_rlc", seed, nullptr, group, true}, codes, nullptr, nullptr);
+                          RlcCall{"hg_verify_aggregate_msgs_rlc", seed, nullptr, group, true}, codes, nullptr, nullptr);
 }
 
 int hg_verify_aggregate_msgs_rlc_device(hg_ctx* c, const uint8_t* d_pool, size_t pool_len, const uint32_t* d_msg_off,
                                         const uint32_t* d_msg_len, const hg_request* d_reqs, size_t n,
                                         const uint64_t* d_words, const uint8_t* d_sigs, const uint8_t seed[32],
                                         uint32_t group, int32_t* d_codes, void* stream) {
-  if (!c || !seed || !group_ok(group) || (n && (!d_msg_off || !d_msg_len || !d_reqs || !d_sigs || !d_codes)) ||
+  if (!c || !seed || !rlc_group_ok(group) || (n && (!d_msg_off || !d_msg_len || !d_reqs || !d_sigs || !d_codes)) ||
       (!d_pool && pool_len) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (n == 0) return HG_OK;
   HG_CHECK(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   bool ran = false;
   return mrlc_device_locked(c, MsgBatch{d_pool, pool_len, d_msg_off, d_msg_len, d_reqs, n, d_words, d_sigs, d_codes},
-                            MrlcCall{"hg_verify_aggregate_msgs_rlc_device", seed, nullptr, group, true}, &ran, s);
+                            RlcCall{"hg_verify_aggregate_msgs_rlc_device", seed, nullptr, group, true}, &ran, s);
 }
 
 int hg_verify_multisig_msgs_rlc(hg_ctx* c, const uint8_t* pool, size_t pool_len, const uint32_t* msg_off,
                                 const uint32_t* msg_len, const uint32_t* bitlens, const uint32_t* word_offsets,
                                 size_t n, const uint64_t* words, size_t nwords, const uint8_t* sigs,
                                 const uint8_t seed[32], uint32_t group, int32_t* codes) {
-  if (!c || !seed || !group_ok(group) ||
+  if (!c || !seed || !rlc_group_ok(group) ||
       (n && (!msg_off || !msg_len || !bitlens || !word_offsets || !sigs || !codes)) || (!pool && pool_len) ||
       (!words && nwords) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (n == 0) return HG_OK;
   // crypto.go:121-124: the bitset must span the registry (bitlen != N is the
   // level error of the request [0, N), renamed on the host); the rest is verifySignature
   const std::vector<hg_request> reqs = multisig_requests(c, bitlens, word_offsets, n);
   int rc = mrlc_host_locked(c, pool, pool_len, msg_off, msg_len,
                             HostBatch{"hg_verify_multisig_msgs_rlc", reqs.data(), n, words, nwords, sigs}, nullptr,
-                            MrlcCall{"hg_verify_multisig_msgs_rlc", seed, nullptr, group, true}, codes, nullptr,
+                            RlcCall{"hg_verify_multisig_msgs_rlc", seed, nullptr, group, true}, codes, nullptr,
                             nullptr);
   if (rc) return rc;
   for (size_t i = 0; i < n; i++)
@@ -279,7 +299,7 @@ int hg_debug_msgs_rlc_groups(hg_ctx* c, const uint8_t* pool, size_t pool_len, co
                              const uint32_t* msg_len, const hg_request* reqs, size_t n, const uint64_t* words,
                              size_t nwords, const uint8_t* sigs, const uint64_t* coeffs, uint32_t group,
                              int32_t* codes, int32_t* group_codes, uint32_t* group_live) {
-  if (!c || !group_ok(group) ||
+  if (!c || !rlc_group_ok(group) ||
       (n && (!msg_off || !msg_len || !reqs || !sigs || !coeffs || !codes || !group_codes || !group_live)) ||
       (!pool && pool_len) || (!words && nwords) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
@@ -287,7 +307,7 @@ int hg_debug_msgs_rlc_groups(hg_ctx* c, const uint8_t* pool, size_t pool_len, co
   std::lock_guard<std::mutex> g(c->mu);
   return mrlc_host_locked(c, pool, pool_len, msg_off, msg_len,
                           HostBatch{"hg_debug_msgs_rlc_groups", reqs, n, words, nwords, sigs}, coeffs,
-                          MrlcCall{"hg_debug_msgs_rlc_groups", nullptr, nullptr, group, false}, codes, group_codes,
+                          RlcCall{"hg_debug_msgs_rlc_groups", nullptr, nullptr, group, false}, codes, group_codes,
                           group_live);
 }
 

@@ -6,18 +6,35 @@
 // the comparison; the live members of a group that fails go through the exact
 // path's stored pairing and comparison. A context that would not take a GT flow
 // runs the exact path's table-less flow instead.
-#include <cstring>
-
 #include "hg_aggregate.h"
 
-namespace {
+// ---------------------------------------------------------------- what the three combined forms share (hg_aggregate.h)
+void rlc_clear_stats(hg_ctx* c) { c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0; }
 
-struct RlcCall {
-  const uint8_t* seed;       // 32 bytes, or
-  const uint64_t* d_coeffs;  // the probes' coefficients (device)
-  uint32_t group;
-  bool recheck;  // false: hg_debug_rlc_groups stops after the group comparison
-};
+int rlc_read_stats(hg_ctx* c, const RlcCall& call, size_t n, hipStream_t s, RlcHdr* h) {
+  // the one read-back: how many checks the failed groups hold sizes their launch
+  RlcHdr got{};
+  HG_CHECK(c, hipMemcpyAsync(&got, c->ws.rlc_hdr.p, sizeof got, hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, hipStreamSynchronize(s));
+  *h = got;
+  c->rlc_stats[0] = got.groups;
+  c->rlc_stats[1] = got.groups_failed;
+  c->rlc_stats[2] = got.failed_members;
+  if (got.failed_members > n) {
+    c->err = std::string(call.who) + ": inconsistent failed-member count";
+    return HG_ERR_DEVICE;
+  }
+  return HG_OK;
+}
+
+int rlc_copy_groups(hg_ctx* c, size_t ng, int32_t* group_codes, uint32_t* group_live, hipStream_t s) {
+  HG_CHECK(c, hipMemcpyAsync(group_codes, c->ws.rlc_gcodes.p, ng * 4, hipMemcpyDeviceToHost, s));
+  HG_CHECK(c, hipMemcpyAsync(group_live, c->ws.rlc_glive.p, ng * 4, hipMemcpyDeviceToHost, s));
+  return HG_OK;
+}
+
+// ---------------------------------------------------------------- hg_verify_aggregate_rlc* and the probes
+namespace {
 
 hipError_t rlc_ensure(Ws& ws, size_t n, size_t ng) {
   hipError_t e = hipSuccess;
@@ -28,12 +45,6 @@ hipError_t rlc_ensure(Ws& ws, size_t n, size_t ng) {
   grow(ws.rlc_glive, ng), grow(ws.rlc_gcodes, ng), grow(ws.rlc_gpts, ng), grow(ws.rlc_gsigs, ng * 64);
   grow(ws.rlc_p, ng * kRlcBits), grow(ws.rlc_z, ng), grow(ws.rlc_hdr, 1);
   return e;
-}
-
-RlcSeed seed_of(const uint8_t* seed) {
-  RlcSeed sd{};
-  if (seed) memcpy(sd.b, seed, 32);
-  return sd;
 }
 
 // the G1 side's second half: per group the marshal of sum r_i sig_i over the checks whose code is HG_OK
@@ -68,12 +79,12 @@ int rlc_recheck(hg_ctx* c, const AggBatch& b, Ws& ws, const GtWork& gw, uint32_t
 // ran (false: the exact path did, or nothing for a probe).
 int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* ran, hipStream_t s) {
   *ran = false;
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (!c->cur.has_msg) {
     c->err = "hg_set_message was not called";
     return HG_ERR_ARG;
   }
-  const size_t n = b.n, ng = (n + call.group - 1) / call.group;
+  const size_t n = b.n, ng = rlc_groups(n, call.group);
   Ws& ws = c->ws;
   Submission sub(c, s);
   HG_CHECK(c, sub.start());
@@ -85,7 +96,7 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
   if (level == 0) {
     // no GT flow: the exact path's fold in G2 and two-pairing check
     if (!call.recheck) {
-      c->err = "hg_debug_rlc_groups: the context has no GT tables to combine over";
+      c->err = std::string(call.who) + ": the context has no GT tables to combine over";
       return HG_ERR_ARG;
     }
     HG_CHECK(c, ws_ensure(ws, n, kWsG2Fold | kWsVerify | (b.lvl ? 0 : kWsLevel), {}, sig_form_ws_bytes(form, (int)n)));
@@ -107,7 +118,7 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
   HG_CHECK(c, ws_ensure(ws, n, kWsVerify | kWsPairing | (beside ? kWsSide : 0), {}, sig_form_ws_bytes(gform, (int)ng)));
   HG_CHECK(c, rlc_ensure(ws, n, ng));
   PhaseTimer all(c, HG_PHASE_SUBMIT, s);
-  launch_rlc_prep(seed_of(call.seed), call.d_coeffs, (int)n, (int)ng, ws.rlc_r.p, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
+  launch_rlc_prep(rlc_seed_of(call.seed), call.d_coeffs, (int)n, (int)ng, ws.rlc_r.p, ws.rlc_gcodes.p, ws.rlc_hdr.p, s);
   gt_prologue(c, b, ws, gw, s);
   hipStream_t g1s = beside ? (hipStream_t)ws.side : s;
   if (beside) {
@@ -135,21 +146,10 @@ int rlc_device_locked(hg_ctx* c, const AggBatch& b, const RlcCall& call, bool* r
   if (rc) return rc;
   *ran = true;
   if (call.recheck) {
-    // the one read-back: how many checks the failed groups hold sizes their launch
     RlcHdr h{};
-    HG_CHECK(c, hipMemcpyAsync(&h, ws.rlc_hdr.p, sizeof h, hipMemcpyDeviceToHost, s));
-    HG_CHECK(c, hipStreamSynchronize(s));
-    c->rlc_stats[0] = h.groups;
-    c->rlc_stats[1] = h.groups_failed;
-    c->rlc_stats[2] = h.failed_members;
-    if (h.failed_members > n) {
-      c->err = "hg_verify_aggregate_rlc: inconsistent failed-member count";
-      return HG_ERR_DEVICE;
-    }
-    if (h.failed_members) {
-      rc = rlc_recheck(c, b, ws, gw, call.group, h.failed_members, s);
-      if (rc) return rc;
-    }
+    rc = rlc_read_stats(c, call, n, s, &h);
+    if (rc == HG_OK && h.failed_members) rc = rlc_recheck(c, b, ws, gw, call.group, h.failed_members, s);
+    if (rc) return rc;
   }
   all.stop();
   rc = check_launch(c);
@@ -176,14 +176,11 @@ int rlc_host_locked(hg_ctx* c, const HostBatch& h, const uint64_t* coeffs, const
   rc = rlc_device_locked(c, b, call, &ran, c->stream);
   if (rc) return rc;
   if (group_codes && ran) {
-    const size_t ng = (h.n + call.group - 1) / call.group;
-    HG_CHECK(c, hipMemcpyAsync(group_codes, c->ws.rlc_gcodes.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
-    HG_CHECK(c, hipMemcpyAsync(group_live, c->ws.rlc_glive.p, ng * 4, hipMemcpyDeviceToHost, c->stream));
+    rc = rlc_copy_groups(c, rlc_groups(h.n, call.group), group_codes, group_live, c->stream);
+    if (rc) return rc;
   }
   return st.close(h, b.codes, codes, nullptr);
 }
-
-bool rlc_group_ok(uint32_t group) { return group >= 1 && group <= kRlcMaxGroup; }
 
 }  // namespace
 
@@ -194,10 +191,10 @@ int hg_verify_aggregate_rlc(hg_ctx* c, const hg_request* reqs, size_t n, const u
   if (!c || !seed || !rlc_group_ok(group) || (n && (!reqs || !sigs || !codes)) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (n == 0) return HG_OK;
   return rlc_host_locked(c, HostBatch{"hg_verify_aggregate_rlc", reqs, n, words, nwords, sigs}, nullptr,
-                         RlcCall{seed, nullptr, group, true}, codes, nullptr, nullptr);
+                         RlcCall{"hg_verify_aggregate_rlc", seed, nullptr, group, true}, codes, nullptr, nullptr);
 }
 
 int hg_verify_aggregate_rlc_device(hg_ctx* c, const hg_request* d_reqs, size_t n, const uint64_t* d_words,
@@ -206,13 +203,14 @@ int hg_verify_aggregate_rlc_device(hg_ctx* c, const hg_request* d_reqs, size_t n
   if (!c || !seed || !rlc_group_ok(group) || (n && (!d_reqs || !d_sigs || !d_codes)) || n > (size_t)INT32_MAX)
     return HG_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  c->rlc_stats[0] = c->rlc_stats[1] = c->rlc_stats[2] = 0;
+  rlc_clear_stats(c);
   if (n == 0) return HG_OK;
   HG_CHECK(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   bool ran = false;
-  return rlc_device_locked(c, AggBatch{d_reqs, n, d_words, d_sigs, d_codes}, RlcCall{seed, nullptr, group, true}, &ran,
-                           s);
+  // who: hg_last_error names the host variant for both, as it always has
+  return rlc_device_locked(c, AggBatch{d_reqs, n, d_words, d_sigs, d_codes},
+                           RlcCall{"hg_verify_aggregate_rlc", seed, nullptr, group, true}, &ran, s);
 }
 
 int hg_rlc_stats(hg_ctx* c, uint64_t* groups, uint64_t* groups_failed, uint64_t* rechecked) {
@@ -237,7 +235,7 @@ int hg_debug_rlc_g1(hg_ctx* c, const uint8_t* sigs, size_t n, const uint64_t* co
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HG_CHECK(c, hipSetDevice(c->device));
-  const size_t ng = (n + group - 1) / group;
+  const size_t ng = rlc_groups(n, group);
   Ws& ws = c->ws;
   hipStream_t s = c->stream;
   HG_CHECK(c, c->bytes_b.ensure(n * 64));
@@ -267,7 +265,8 @@ int hg_debug_rlc_groups(hg_ctx* c, const hg_request* reqs, size_t n, const uint6
   if (n == 0) return HG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   return rlc_host_locked(c, HostBatch{"hg_debug_rlc_groups", reqs, n, words, nwords, sigs}, coeffs,
-                         RlcCall{nullptr, nullptr, group, false}, codes, group_codes, group_live);
+                         RlcCall{"hg_debug_rlc_groups", nullptr, nullptr, group, false}, codes, group_codes,
+                         group_live);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@ from tests import test_gpu_aggregate_msgs as A
 pytestmark = pytest.mark.gpu
 
 HG_OK, SIG_INVALID, HASH_EOF, LEVEL, SIG_UNMARSHAL, EMPTY_AGG, MULTI_SIZES = 0, 1, 2, 3, 5, 6, 13
+PHASE_VERIFY, PHASE_AGGREGATE, PHASE_SUBMIT = 0, 1, 2  # enum hg_phase
 N = 67
 POOL = 150
 SEED = bytes(range(7, 39))
@@ -422,3 +423,27 @@ def test_context_state_is_untouched(torch_first):
         assert state() == before
     finally:
         e.close()
+
+
+# ---------------------------------------------------------------- 9. phase intervals
+def test_phase_interval_counts(ctx):
+    """What hg_timing_read_phase reports for one combined call: 13 requests in
+    groups of 4 (three full groups and a ragged one), request 5 with an invalid
+    signature, so the recheck runs inside the intervals. One submission, one
+    aggregate interval (the G2 fold), one verify interval (the combination and
+    the recheck)."""
+    e = ctx.eng
+    cases, sigs = _batch(ctx, 13, {5: tampered})
+    reqs, words = A._pack(cases)
+    e.timing_enable(True)
+    try:
+        for ph in range(3):
+            e.timing_read_phase(ph)
+        got = e.verify_aggregate_msgs_rlc([k.msg for k in cases], reqs, words, sigs, seed=SEED, group=4)
+        read = [e.timing_read_phase(ph) for ph in (PHASE_SUBMIT, PHASE_AGGREGATE, PHASE_VERIFY)]
+    finally:
+        e.timing_enable(False)
+    print("submit, aggregate, verify (ms, intervals):", read)
+    assert [i for i in range(13) if got[i]] == [5] and got[5] == SIG_INVALID and e.rlc_stats() == (4, 1, 4)
+    assert [k for _, k in read] == [1, 1, 1]
+    assert all(ms > 0 for ms, _ in read)

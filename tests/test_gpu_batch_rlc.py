@@ -26,6 +26,7 @@ from tests import _msgs_fixtures as M
 pytestmark = pytest.mark.gpu
 
 HG_OK, SIG_INVALID, HASH_EOF, PK_UNMARSHAL, SIG_UNMARSHAL, CF_MALFORMED, HG_ERR_ARG = 0, 1, 2, 4, 5, 8, 100
+PHASE_VERIFY, PHASE_AGGREGATE, PHASE_SUBMIT = 0, 1, 2  # enum hg_phase
 FLAVOR_ID = {"go": 0, "cf": 1}
 POOL = 150
 SEED = bytes(range(11, 43))
@@ -449,3 +450,28 @@ def test_device_forms_equal_the_host_forms(eng, form):
             assert eng.batch_rlc_stats() == stats
     finally:
         eng.set_fold_overlap(True)
+
+
+# ---------------------------------------------------------------- 8. phase intervals
+@pytest.mark.parametrize("form", ["one", "msgs"])
+def test_phase_interval_counts(eng, form):
+    """What hg_timing_read_phase reports for one combined call: 13 checks in
+    groups of 4 (three full groups and a ragged one), check 5 with an invalid
+    signature, so the recheck runs inside the intervals. One submission, no
+    aggregate interval (nothing is folded), one verify interval (the combination
+    and the recheck)."""
+    cases = pool_cases(form, 13)
+    cases[5] = (cases[5][0], cases[5][1], sign(6, cases[5][0]))
+    eng.timing_enable(True)
+    try:
+        for ph in range(3):
+            eng.timing_read_phase(ph)
+        got = run_rlc(eng, form, cases, 4)
+        read = [eng.timing_read_phase(ph) for ph in (PHASE_SUBMIT, PHASE_AGGREGATE, PHASE_VERIFY)]
+    finally:
+        eng.timing_enable(False)
+    print("submit, aggregate, verify (ms, intervals):", read)
+    assert [i for i in range(13) if got[i]] == [5] and got[5] == SIG_INVALID
+    assert eng.batch_rlc_stats() == (4, 1, 4, 0)
+    assert [k for _, k in read] == [1, 0, 1]
+    assert all((ms > 0) == (k > 0) for ms, k in read)

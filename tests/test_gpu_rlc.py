@@ -257,3 +257,28 @@ def test_without_tables_the_exact_path_runs(st):
     finally:
         st.eng.set_aggregate_level(level)
     _check(st, reqs, words, sigs, 4, SEEDS[0], stats=(2, 1, 4))
+
+
+# ------------------------------------------------------------------ 5. phase intervals
+def test_phase_interval_counts(st):
+    """What hg_timing_read_phase reports for one combined call at a GT level: 13
+    checks in groups of 4 (three full groups and a ragged one), check 5 with an
+    invalid signature, so the recheck runs inside the intervals. One submission;
+    two aggregate intervals (the GT fold, the combination's GT stages); two
+    pairing intervals (the groups', the recheck's)."""
+    e = st.eng
+    reqs, words, sigs = _valid_batch(st, 13, seed=13)
+    _put(sigs, 5, R.g1_add(_get(sigs, 5), G1))
+    e.timing_enable(True)
+    try:
+        for ph in range(3):
+            e.timing_read_phase(ph)
+        got = e.verify_aggregate_rlc(reqs, words, bytes(sigs), seed=SEEDS[0], group=4)
+        read = [e.timing_read_phase(ph) for ph in (_lib.HG_PHASE_SUBMIT, _lib.HG_PHASE_AGGREGATE,
+                                                   _lib.HG_PHASE_VERIFY)]
+    finally:
+        e.timing_enable(False)
+    print("submit, aggregate, verify (ms, intervals):", read)
+    assert [i for i in range(13) if got[i]] == [5] and got[5] == INVALID and e.rlc_stats() == (4, 1, 4)
+    assert [k for _, k in read] == [1, 2, 2]
+    assert all(ms > 0 for ms, _ in read)
