@@ -136,6 +136,7 @@ SIGNATURES = {
     "hg_sig_pairing_device": (_I, [_P, _P, _SZ, _P, _I, _P]),
     "hg_debug_fp12": (_I, [_P, _I, _P, _P, _SZ, _P]),
     "hg_debug_xinst": (_I, [_P, _I, _I, _P, _SZ, _P, ctypes.POINTER(_I)]),
+    "hg_debug_field": (_I, [_P, _I, _P, _SZ, _P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "hg_timing_enable": (_I, [_P, _I]),
     "hg_timing_read": (_I, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "hg_timing_read_phase": (_I, [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),

@@ -20,7 +20,8 @@ OUT_DIR = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT_DIR, "libhandel_gpu.so")
 DIAG_LIB = os.path.join(OUT_DIR, "libhandel_gpu_diag.so")
 SOURCES = ["bn256_verify.hip", "bn256_pair.hip", "bn256_kernels.hip", "bn256_gt.hip", "bn256_gttab.hip",
-           "bn256_sig16.hip", "bn256_sig12.hip", "bn256_sigw2.hip", "bn256_xprobe.hip", "bn256_xprobew2.hip", "hg_api.cpp",
+           "bn256_sig16.hip", "bn256_sig12.hip", "bn256_sigw2.hip", "bn256_xprobe.hip", "bn256_xprobew2.hip", "bn256_fprobe.hip",
+           "hg_api.cpp",
            "hg_aggregate.cpp", "hg_gttables.cpp", "hg_lanes.cpp", "hg_intake.cpp", "hg_batcher.cpp", "hg_packets.hip", "hg_service.cpp", "hg_stores.hip",
            "hg_merge.hip", "bn256_msgs.hip", "bn256_aggmsgs.hip", "hg_msgs.cpp", "bn256_rlc.hip", "hg_rlc.cpp",
            "bn256_msgsrlc.hip", "hg_msgs_rlc.cpp", "bn256_batchrlc.hip", "hg_batch_rlc.cpp"]

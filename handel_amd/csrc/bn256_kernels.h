@@ -142,5 +142,9 @@ int xprobe_instances();
 int xprobe_region_elems(int inst, int form);
 void launch_xprobe(int inst, int form, const uint32_t* in, int n, uint32_t* out, hipStream_t s);
 void launch_fp_mul(const uint32_t* a, const uint32_t* b, int n, uint32_t* out, hipStream_t s);
+// the per-thread primitive probe (bn256_fprobe.hip): the words of one case of op in and out
+// (false: no such op), one launch of op on n cases of raw limbs
+bool fprobe_words(int op, int* in_words, int* out_words);
+void launch_fprobe(int op, const uint32_t* in, int n, uint32_t* out, hipStream_t s);
 
 }  // namespace hg

@@ -548,6 +548,32 @@ int hg_debug_xinst(hg_ctx* c, int inst, int form, const uint32_t* in, size_t n, 
   return HG_OK;
 }
 
+// One per-thread primitive of bn256_fp.h / bn256_curve.h on n cases of raw limbs (bn256_fprobe.hip)
+int hg_debug_field(hg_ctx* c, int op, const uint32_t* in, size_t n, uint32_t* out, int* in_words, int* out_words) {
+  if (!c) return HG_ERR_ARG;
+  int wi = 0, wo = 0;
+  if (!fprobe_words(op, &wi, &wo)) return HG_ERR_ARG;
+  if ((n && (!in || !out)) || n > (size_t)1 << 20) return HG_ERR_ARG;
+  if (in_words) *in_words = wi;
+  if (out_words) *out_words = wo;
+  if (n == 0) return HG_OK;
+  const size_t bytes_in = n * (size_t)wi * 4, bytes_out = n * (size_t)wo * 4;
+  std::lock_guard<std::mutex> g(c->mu);
+  HG_CHECK(c, hipSetDevice(c->device));
+  HG_CHECK(c, c->bytes_a.ensure(bytes_in + bytes_out));
+  uint8_t* d = c->bytes_a.p;
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(d, in, bytes_in, hipMemcpyHostToDevice, c->stream));
+  launch_fprobe(op, (const uint32_t*)d, (int)n, (uint32_t*)(d + bytes_in), c->stream);
+  int rc = check_launch(c);
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpyAsync(out, d + bytes_in, bytes_out, hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+
 // kernel: a SigForm by its number (bn256_sigform.h), whatever sig_form() would choose
 int hg_sig_pairing_device(hg_ctx* c, const uint8_t* d_sigs, size_t n, uint8_t* d_fe, int kernel, void* stream) {
   if (!c || (n && (!d_sigs || !d_fe)) || n > (size_t)INT32_MAX || kernel < 0 || kernel > 4) return HG_ERR_ARG;

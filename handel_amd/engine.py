@@ -804,6 +804,26 @@ class Engine:
                                           _ptr(out) if n else None, None), "hg_debug_xinst")
         return out
 
+    def field_words(self, op: int) -> Tuple[int, int]:
+        """Words of one case of per-thread probe `op` going in and coming out (hg_debug_field with n = 0)."""
+        wi, wo = ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.hg_debug_field(self.ctx, int(op), None, 0, None, ctypes.byref(wi), ctypes.byref(wo)),
+                    "hg_debug_field")
+        return wi.value, wo.value
+
+    def field_op(self, op: int, cases: np.ndarray) -> np.ndarray:
+        """One per-thread primitive of bn256_fp.h / bn256_curve.h on raw limbs
+        (hg_debug_field): cases is a uint32 array (n, in_words), the result (n, out_words)."""
+        a = np.ascontiguousarray(cases, dtype=np.uint32)
+        wi, wo = self.field_words(op)
+        if a.ndim != 2 or a.shape[1] != wi:
+            raise ValueError(f"cases of shape {a.shape}, want (n, {wi})")
+        n = a.shape[0]
+        out = np.zeros((n, wo), dtype=np.uint32)
+        self._check(self.L.hg_debug_field(self.ctx, int(op), _ptr(a) if n else None, n, _ptr(out) if n else None,
+                                          None, None), "hg_debug_field")
+        return out
+
     def fp_mul(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.uint32)
         b = np.ascontiguousarray(b, dtype=np.uint32)

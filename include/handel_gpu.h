@@ -539,6 +539,38 @@ int hg_debug_fp12(hg_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_
  * n = 0 only reports region_elems (may be NULL otherwise). n <= 2^20. */
 int hg_debug_xinst(hg_ctx* ctx, int inst, int form, const uint32_t* in, size_t n, uint32_t* out, int* region_elems);
 
+/* Probe of ONE per-thread primitive of bn256_fp.h / bn256_curve.h, for the
+ * bit-exact comparison with an integer reference: one thread per case, the
+ * production function itself. in and out hold n cases of *in_words and
+ * *out_words 32-bit words. An Fp element is ten words, the 26-bit limbs Fp::l
+ * as they are (Montgomery form, R = 2^286; no conversion, no reduction), an
+ * Fp2 is x then y, a Jacobian point x, y, z, an affine point x, y. Operands
+ * are canonical, in [0, p), unless stated. op (words in -> out):
+ *    0 fp_add(a, b)        1 fp_sub(a, b)       2 fp_neg(a)      3 fp_dbl(a)
+ *    4 fp_mul3(a)          5 fp_mul(a, b)       6 fp_sqr(a)      7 fp_inv(a), 0 -> 0
+ *    8 fp_neg_loose(a): normalised limbs of p - a, so p for a = 0
+ *    9 fp_add_loose(a, b): the limb-wise sums
+ *   10 fp_to_mont(words_to_limbs(w)): 8 LE words of any integer < 2^256 -> 10
+ *   11 limbs_to_words(fp_from_mont(a)): 10 -> 8 LE words
+ *   12 fp_from_be: word 0 = a byte offset k in 0..3, words 1..9 = a 36-byte
+ *      buffer holding 32 big-endian bytes (any integer < 2^256) at byte k; k = 0
+ *      takes be_to_words' dword path, the others its byte path. 10 -> 12: the
+ *      element, ge (the integer is >= p), nz (some byte is nonzero)
+ *   13 fp_to_be(a): 10 -> 8 words holding the 32 big-endian bytes
+ *   14 f2_mul(a, b)  15 f2_sqr(a)  16 f2_muls(a, s in Fp)  17 f2_mul_xi(a)
+ *   18 f2_inv(a), 0 -> 0           19 f2_sub(a, b)  20 f2_neg(a)  21 f2_conj(a)
+ *   22 g1_double(P)  23 g1_add(P, Q)  24 g1_madd(P, affine Q)  25 g1_on_curve(x, y) -> 1 word
+ *   26 g1_affine(P), infinity -> (0, 0)
+ *   27 g2_double(P)  28 g2_add(P, Q)  29 g2_madd(P, affine Q)  30 g2_add_affine(P, affine Q)
+ *   31 g2_on_curve(x, y) -> 1 word    32 g2_affine(P), infinity -> (0, 0)
+ * Jacobian operands: coordinates in [0, p), on the curve (X, Y, Z with
+ * Y^2 = X^3 + b Z^6) or at infinity (Z = 0, X and Y anything); the affine
+ * operand of 24, 29, 30 is a finite point of the curve; 25, 26, 31, 32 take
+ * any canonical coordinates. An unknown op, NULL in or out with n > 0, or
+ * n > 2^20: HG_ERR_ARG, nothing runs, out and the word counts untouched.
+ * n = 0 only reports the word counts (either may be NULL). */
+int hg_debug_field(hg_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out, int* in_words, int* out_words);
+
 /* Kernel probe of the GT path's signature side (bench.py per-kernel
  * roofline, the GPU suite's cross-kernel check): d_fe[r] (480 bytes, the
  * engine's internal GT layout) = FE(Miller(G2Base at -sig_r)) for the n
