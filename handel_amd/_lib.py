@@ -53,6 +53,7 @@ HG_MERGE_ERR_INDIVIDUAL = 4
 HG_MERGE_ERR_ROW = 5
 HG_COMBINED_EMPTY = 1
 HG_COMBINED_ERR_MISSING = 2
+HG_GT_LAYOUT_WORDS = 54
 HG_ERR_ARG = 100
 HG_ERR_DEVICE = 101
 
@@ -137,6 +138,9 @@ SIGNATURES = {
     "hg_debug_fp12": (_I, [_P, _I, _P, _P, _SZ, _P]),
     "hg_debug_xinst": (_I, [_P, _I, _I, _P, _SZ, _P, ctypes.POINTER(_I)]),
     "hg_debug_field": (_I, [_P, _I, _P, _SZ, _P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "hg_debug_gt_layout": (_I, [_P, _P]),
+    "hg_debug_gt_entries": (_I, [_P, _I, _SZ, _SZ, _P]),
+    "hg_debug_gt_fold": (_I, [_P, _P, _SZ, _P, _SZ, _I, _P, _P]),
     "hg_timing_enable": (_I, [_P, _I]),
     "hg_timing_read": (_I, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "hg_timing_read_phase": (_I, [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),

@@ -415,6 +415,87 @@ int hg_verify_multisig(hg_ctx* c, const uint32_t* bitlens, const uint32_t* word_
   return HG_OK;
 }
 
+// The fold alone, for the value-level tests: submission_level's window width
+// and form over the tables as built, `chunk` terms per chunk, every workspace
+// local and sized for that chunk (FoldCaps and ensure_gt_fold follow gt_chunk()).
+int hg_debug_gt_fold(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords, int chunk,
+                     uint32_t* y, int32_t* codes) {
+  if (!c || !reqs || !y || !codes || (!words && nwords) || n == 0 || n > ((size_t)1 << 20) || chunk < 1 || chunk > 64)
+    return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->cur.gt_level < 1 || c->nreg == 0) {
+    c->err = "hg_debug_gt_fold: no tables are built";
+    return HG_ERR_ARG;
+  }
+  std::vector<int32_t> lvl(n);
+  int rc = check_host_requests(c, HostBatch{"hg_debug_gt_fold", reqs, n, words, nwords, nullptr}, lvl.data(), nullptr);
+  if (rc) return rc;
+  // capacities: at most 8 nonzero windows per registry-aligned word of the
+  // range (either width, the shift included) and the block term
+  size_t terms = 0, chunks = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (lvl[i] != HG_OK) continue;
+    const size_t m = 8 * (((size_t)reqs[i].bitlen + 15 + 63) / 64) + 1;
+    terms += m;
+    chunks += (m + chunk - 1) / chunk;
+  }
+  if (terms > (size_t)INT32_MAX) return HG_ERR_ARG;
+  HG_CHECK(c, hipSetDevice(c->device));
+  DevBuf<hg_request> d_reqs;
+  DevBuf<uint64_t> d_words;
+  DevBuf<int32_t> d_codes;
+  DevBuf<GtReq> plan;
+  DevBuf<GtHdr> hdr;
+  DevBuf<uint32_t> d_terms;
+  DevBuf<int2> ord;
+  DevBuf<int> multi;
+  DevBuf<Gt> partial, d_y;
+  HG_CHECK(c, d_reqs.ensure(n));
+  HG_CHECK(c, d_words.ensure(nwords ? nwords : 1));
+  HG_CHECK(c, d_codes.ensure(n));
+  HG_CHECK(c, plan.ensure(n));
+  HG_CHECK(c, hdr.ensure(1));
+  HG_CHECK(c, d_terms.ensure(terms ? terms : 1));
+  HG_CHECK(c, ord.ensure(chunks ? chunks : 1));
+  HG_CHECK(c, multi.ensure(2 * n));
+  HG_CHECK(c, partial.ensure(chunks ? chunks : 1));
+  HG_CHECK(c, d_y.ensure(n));
+  GtWork w{};
+  w.plan = plan.p;
+  w.hdr = hdr.p;
+  w.terms = d_terms.p;
+  w.ord = ord.p;
+  w.cap = (int)(chunks ? chunks : 1);
+  w.multi = multi.p;
+  w.partial = partial.p;
+  const size_t need = (chunks + kGtChunkTeams - 1) / kGtChunkTeams;
+  w.chunk_grid = (int)(need < 4096 ? (need ? need : 1) : 4096);
+  w.chunk = chunk;
+  // submission_level's rule over the built tables: the pinned level if lower, but a torus set has one fold table
+  int level = c->cur.gt_level;
+  if (c->pinned_level >= 1 && c->pinned_level < level) level = c->pinned_level;
+  if (c->cur.gt_level == 2 && c->cur.torus) level = 2;
+  w.win_bits = level == 2 ? 16 : 8;
+  w.torus = level == 2 && c->cur.torus;
+  hipStream_t s = c->stream;
+  Submission sub(c, s);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(d_reqs.p, reqs, n * sizeof(hg_request), hipMemcpyHostToDevice, s));
+  if (nwords) HG_CHECK(c, hipMemcpyAsync(d_words.p, words, nwords * 8, hipMemcpyHostToDevice, s));
+  HG_CHECK(c, hipMemsetAsync(d_y.p, 0, n * sizeof(Gt), s));
+  launch_aggmsgs_levels(d_reqs.p, (int)n, (uint32_t)c->nreg, d_codes.p, s);
+  launch_gt_fold(d_reqs.p, (int)n, d_words.p, d_codes.p, (int)c->nreg, c->block_levels,
+                 w.win_bits == 16 ? c->cur.gt_win.p : c->cur.gt_w8.p, c->cur.gt_blk.p, c->gt_bi, w, d_y.p, true, s);
+  rc = check_launch(c);
+  HG_CHECK(c, sub.finish());
+  // the local workspaces are freed on return: nothing may still be running
+  HG_CHECK(c, hipStreamSynchronize(s));
+  if (rc) return rc;
+  HG_CHECK(c, hipMemcpy(y, d_y.p, n * sizeof(Gt), hipMemcpyDeviceToHost));
+  HG_CHECK(c, hipMemcpy(codes, d_codes.p, n * 4, hipMemcpyDeviceToHost));
+  return HG_OK;
+}
+
 int hg_aggregate_pk(hg_ctx* c, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords,
                     uint8_t* agg_pk_out, int32_t* codes) {
   if (!c || (n && (!reqs || !agg_pk_out || !codes)) || n > (size_t)INT32_MAX) return HG_ERR_ARG;

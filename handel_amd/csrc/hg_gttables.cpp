@@ -274,4 +274,54 @@ int hg_prepare_aggregate_level(hg_ctx* c, int level) {
   return prepare_aggregate_locked(c, level);
 }
 
+// The current message's table set as built (the value-level tests read it back)
+int hg_debug_gt_layout(hg_ctx* c, int32_t* out) {
+  if (!c || !out) return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->cur.gt_level < 1 || c->nreg == 0) {
+    c->err = "hg_debug_gt_layout: no tables are built";
+    return HG_ERR_ARG;
+  }
+  int cnt[24] = {0};
+  gt_block_count(c, cnt);
+  memset(out, 0, HG_GT_LAYOUT_WORDS * sizeof(int32_t));
+  out[0] = c->cur.gt_level;
+  out[1] = c->cur.gt_level == 2 && c->cur.torus ? 1 : 0;
+  out[2] = (int32_t)c->nreg;
+  out[3] = (int32_t)((c->nreg + 7) / 8);
+  out[4] = (int32_t)((c->nreg + 15) / 16);
+  out[5] = c->block_levels < 23 ? c->block_levels : 23;
+  for (int k = 4; k <= out[5]; k++) {
+    out[6 + k] = c->gt_bi.base[k];
+    out[30 + k] = cnt[k];
+  }
+  return HG_OK;
+}
+
+int hg_debug_gt_entries(hg_ctx* c, int table, size_t first, size_t count, uint32_t* out) {
+  if (!c || !out) return HG_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  const Gt* src = nullptr;
+  size_t have = 0;
+  if (c->cur.gt_level >= 1 && c->nreg > 0) {
+    if (table == HG_GT_TABLE_KEYS) src = c->cur.gt_key.p, have = c->nreg;
+    else if (table == HG_GT_TABLE_WIN8) src = c->cur.gt_w8.p, have = (c->nreg + 7) / 8 * 256;
+    else if (table == HG_GT_TABLE_BLOCKS) src = c->cur.gt_blk.p, have = gt_block_count(c, nullptr);
+    else if (table == HG_GT_TABLE_WIN16 && c->cur.gt_level >= 2) src = c->cur.gt_win.p, have = (c->nreg + 15) / 16 * 65536;
+  }
+  if (!src || first > have || count > have - first) {
+    c->err = "hg_debug_gt_entries: no such table is built, or the range leaves it";
+    return HG_ERR_ARG;
+  }
+  if (count == 0) return HG_OK;
+  HG_CHECK(c, hipSetDevice(c->device));
+  // every build is synchronous or inside a submission this one is ordered after
+  Submission sub(c, c->stream);
+  HG_CHECK(c, sub.start());
+  HG_CHECK(c, hipMemcpyAsync(out, src + first, count * sizeof(Gt), hipMemcpyDeviceToHost, c->stream));
+  HG_CHECK(c, sub.finish());
+  HG_CHECK(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+
 }  // extern "C"

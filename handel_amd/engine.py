@@ -824,6 +824,37 @@ class Engine:
                                           None, None), "hg_debug_field")
         return out
 
+    # hg_debug_gt_entries' tables
+    GT_KEYS, GT_WIN8, GT_WIN16, GT_BLOCKS = 0, 1, 2, 3
+
+    def gt_layout(self) -> dict:
+        """The current message's GT table set as built (hg_debug_gt_layout):
+        level, torus, nreg, nwin8, nwin16 and blocks = {k: (base, count)}."""
+        out = np.zeros(_lib.HG_GT_LAYOUT_WORDS, dtype=np.int32)
+        self._check(self.L.hg_debug_gt_layout(self.ctx, _ptr(out)), "hg_debug_gt_layout")
+        top = int(out[5])
+        return {"level": int(out[0]), "torus": bool(out[1]), "nreg": int(out[2]), "nwin8": int(out[3]),
+                "nwin16": int(out[4]), "blocks": {k: (int(out[6 + k]), int(out[30 + k])) for k in range(4, top + 1)}}
+
+    def gt_entries(self, table: int, first: int, count: int) -> np.ndarray:
+        """count entries from `first` of one GT table, raw (hg_debug_gt_entries): uint32 (count, 120)."""
+        out = np.zeros((int(count), 120), dtype=np.uint32)
+        self._check(self.L.hg_debug_gt_entries(self.ctx, int(table), int(first), int(count), _ptr(out)),
+                    "hg_debug_gt_entries")
+        return out
+
+    def gt_fold(self, reqs: np.ndarray, words: np.ndarray, chunk: int):
+        """The GT fold alone over the built tables in `chunk` terms per chunk
+        (hg_debug_gt_fold): (y uint32 (n, 120), codes)."""
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        n = len(reqs)
+        y = np.zeros((n, 120), dtype=np.uint32)
+        codes = np.zeros(n, dtype=np.int32)
+        self._check(self.L.hg_debug_gt_fold(self.ctx, _ptr(reqs), n, _ptr(words) if len(words) else None, len(words),
+                                            int(chunk), _ptr(y), _ptr(codes)), "hg_debug_gt_fold")
+        return y, codes
+
     def fp_mul(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.uint32)
         b = np.ascontiguousarray(b, dtype=np.uint32)

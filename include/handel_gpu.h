@@ -571,6 +571,39 @@ int hg_debug_xinst(hg_ctx* ctx, int inst, int form, const uint32_t* in, size_t n
  * n = 0 only reports the word counts (either may be NULL). */
 int hg_debug_field(hg_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out, int* in_words, int* out_words);
 
+/* Read-back of the GT path's key side, for the value-level comparison with
+ * g^(sum of k_i): the current message's table set as the kernels left it and
+ * the fold's values before any pairing. Nothing here converts or reduces: an
+ * entry is the 120 words Gt::w (element 2k + c of coefficient k of w, c = 0: x;
+ * ten 26-bit limbs of the Montgomery representative; a torus entry holds alpha
+ * in elements 0..5 and zeros after). All three: HG_ERR_ARG without a built
+ * table set (hg_aggregate_tables() == 0), out untouched.
+ *
+ * hg_debug_gt_layout: HG_GT_LAYOUT_WORDS ints: built level, torus flag, nreg,
+ * 8-key windows, 16-key windows, highest block level K, then base[k] and
+ * count[k] for k = 0..23 (block (k, j), 4 <= k <= K, is entry base[k] + j of
+ * the block table; zero outside 4..K). */
+#define HG_GT_LAYOUT_WORDS 54
+#define HG_GT_TABLE_KEYS 0   /* nreg entries */
+#define HG_GT_TABLE_WIN8 1   /* 256 per 8-key window */
+#define HG_GT_TABLE_WIN16 2  /* 65536 per 16-key window (level 2) */
+#define HG_GT_TABLE_BLOCKS 3 /* the sum of count[k] */
+int hg_debug_gt_layout(hg_ctx* ctx, int32_t* out);
+/* count entries from `first` of one table into out (120 words each): a
+ * synchronous device-to-host copy. HG_ERR_ARG for an unknown or unbuilt table
+ * or a range past its end. */
+int hg_debug_gt_entries(hg_ctx* ctx, int table, size_t first, size_t count, uint32_t* out);
+/* The fold alone over the tables as built (the window width and the form an
+ * aggregate submission would use), in `chunk` (1..64) terms per chunk, with
+ * workspaces of its own sized for that chunk: the level check, the plan, the
+ * chunk products and the combine; no pairing, no comparison. y: n x 120 words,
+ * the fold's Y = conj(e(H, aggregate key)) (Fp12 form) or X with
+ * X/conj(X) = Y (torus form), zeros where codes[r] is not HG_OK; codes: HG_OK,
+ * HG_ERR_LEVEL or HG_ERR_EMPTY_AGG. HG_ERR_ARG also for n = 0, n > 2^20, a
+ * chunk outside 1..64 or a request whose words leave the bitset. */
+int hg_debug_gt_fold(hg_ctx* ctx, const hg_request* reqs, size_t n, const uint64_t* words, size_t nwords, int chunk,
+                     uint32_t* y, int32_t* codes);
+
 /* Kernel probe of the GT path's signature side (bench.py per-kernel
  * roofline, the GPU suite's cross-kernel check): d_fe[r] (480 bytes, the
  * engine's internal GT layout) = FE(Miller(G2Base at -sig_r)) for the n

@@ -25,23 +25,13 @@ import pytest
 
 from oracle import bn256_oracle as O
 from tests import _fixtures as F
+from tests._gt_model import fe_bytes as _fe_bytes
 
 pytestmark = pytest.mark.gpu
 
-R_MONT = 1 << 286
 # n -> (index of the signature at infinity, index of the undecodable one)
 CASES = {1: (None, None), 5: (1, None), 6: (2, 4), 11: (3, 7)}
 
-
-def _fe_bytes(f):
-    """A GT value as the kernels store it: element 2k + c (c = 0: x), ten
-    26-bit limbs of the Montgomery representative each."""
-    out = np.zeros((12, 10), dtype=np.uint32)
-    for k, (x, y) in enumerate(f):
-        for c, v in enumerate((x, y)):
-            m = v * R_MONT % O.P
-            out[2 * k + c] = [(m >> (26 * j)) & ((1 << 26) - 1) for j in range(9)] + [m >> 234]
-    return out.reshape(-1).view(np.uint8)
 
 
 def _oracle_fe(sig: bytes, flavor: str):
