@@ -303,3 +303,125 @@ func (s *Stores) CombinedDevice(dQueries unsafe.Pointer, m, wordsStride int, dCo
 	}
 	return nil
 }
+
+// Pool is Handel's queue of parsed signatures kept in device memory across
+// intake steps (hg_stores_pool_*): AppendDevice adds the admitted slots of a
+// parsed batch, StepDevice is one readTodos pass (processing.go:171-220) over
+// the whole queue whose picks come out as a parsed batch for
+// hg_verify_aggregate_device and MergeDevice, the rest staying queued in
+// readTodos' order. Close it before its Stores.
+type Pool struct {
+	s *Stores
+	h *C.hg_pool
+}
+
+// PooledSlot is one queued slot as Read returns it.
+type PooledSlot struct {
+	Origin, Receiver, Level int
+	Individual              bool
+	Mark                    int32 // of the last step; 0 for a slot appended since
+}
+
+// NewPool allocates a pool of capacitySlots slots, workspaces included; no
+// later call allocates device memory.
+func (s *Stores) NewPool(capacitySlots int) (*Pool, error) {
+	var h *C.hg_pool
+	rc := C.hg_stores_pool_create(s.h, C.size_t(capacitySlots), &h)
+	if rc != C.HG_OK {
+		return nil, s.e.fail(rc)
+	}
+	return &Pool{s: s, h: h}, nil
+}
+
+// Close releases the pool's device memory.
+func (p *Pool) Close() {
+	if p.h != nil {
+		C.hg_stores_pool_destroy(p.h)
+		p.h = nil
+	}
+}
+
+// Bytes is the device memory the pool holds.
+func (p *Pool) Bytes() int { return int(C.hg_stores_pool_bytes(p.h)) }
+
+// AppendDevice queues the admitted slots of one hg_parse_packets_device call
+// (its inputs dPkts, n, stride and its outputs; dLive nil or the caller's 2n
+// mask), in Handel's queue order, asynchronous on stream. It fails without
+// appending when 2n slots do not fit.
+func (p *Pool) AppendDevice(dPkts unsafe.Pointer, n, stride int, dReqs, dWords, dSigs, dCodes, dLive,
+	stream unsafe.Pointer) error {
+	rc := C.hg_stores_pool_append_device(p.h, (*C.hg_packet)(dPkts), C.size_t(n), C.size_t(stride),
+		(*C.hg_request)(dReqs), (*C.uint64_t)(dWords), (*C.uint8_t)(dSigs), (*C.int32_t)(dCodes),
+		(*C.uint8_t)(dLive), stream)
+	if rc != C.HG_OK {
+		return p.s.e.fail(rc)
+	}
+	return nil
+}
+
+// SelectCapacity is the number of entries StepDevice writes for k slots per
+// store.
+func (p *Pool) SelectCapacity(k int) int {
+	return int(C.hg_stores_pool_select_capacity(p.h, C.uint32_t(k)))
+}
+
+// StepDevice scores every queued slot against the stores as they are now and
+// writes the k best per store (1 <= k <= 64) as a parsed batch of capacity =
+// SelectCapacity(k) packets: dOutPkts, dSel, dCount, dOutReqs, dOutWords
+// (2*capacity slots), dOutSigs (2*capacity*64 bytes), dOutScores. The picks
+// and the slots of mark <= 0 leave the pool. Asynchronous on stream.
+func (p *Pool) StepDevice(k, capacity int, dOutPkts, dSel, dCount, dOutReqs, dOutWords, dOutSigs, dOutScores,
+	stream unsafe.Pointer) error {
+	rc := C.hg_stores_pool_step_device(p.h, C.uint32_t(k), C.size_t(capacity), (*C.hg_packet)(dOutPkts),
+		(*C.uint32_t)(dSel), (*C.uint32_t)(dCount), (*C.hg_request)(dOutReqs), (*C.uint64_t)(dOutWords),
+		(*C.uint8_t)(dOutSigs), (*C.int32_t)(dOutScores), stream)
+	if rc != C.HG_OK {
+		return p.s.e.fail(rc)
+	}
+	return nil
+}
+
+// Count is the number of slots queued now (synchronous).
+func (p *Pool) Count() (int, error) {
+	var n C.size_t
+	rc := C.hg_stores_pool_count(p.h, &n)
+	if rc != C.HG_OK {
+		return 0, p.s.e.fail(rc)
+	}
+	return int(n), nil
+}
+
+// Read returns the receiver's queued slots in queue order, at most max of
+// them (for tests and diagnosis; synchronous).
+func (p *Pool) Read(receiver, max int) ([]PooledSlot, error) {
+	if max <= 0 {
+		return nil, nil
+	}
+	pkts := make([]C.hg_packet, max)
+	ind := make([]byte, max)
+	marks := make([]int32, max)
+	var n C.size_t
+	rc := C.hg_stores_pool_read(p.h, C.uint32_t(receiver), C.size_t(max), &pkts[0], bytePtr(ind), codePtr(marks), &n)
+	if rc != C.HG_OK {
+		return nil, p.s.e.fail(rc)
+	}
+	m := int(n)
+	if m > max {
+		m = max
+	}
+	out := make([]PooledSlot, m)
+	for i := range out {
+		out[i] = PooledSlot{Origin: int(pkts[i].origin), Receiver: int(pkts[i].receiver), Level: int(pkts[i].level),
+			Individual: ind[i] != 0, Mark: marks[i]}
+	}
+	return out, nil
+}
+
+// Clear empties the pool.
+func (p *Pool) Clear() error {
+	rc := C.hg_stores_pool_clear(p.h)
+	if rc != C.HG_OK {
+		return p.s.e.fail(rc)
+	}
+	return nil
+}

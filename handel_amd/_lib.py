@@ -164,6 +164,15 @@ SIGNATURES = {
     "hg_stores_merge_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "hg_stores_combined_device": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
     "hg_stores_combined": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P]),
+    "hg_stores_pool_create": (_I, [_P, _SZ, ctypes.POINTER(_P)]),
+    "hg_stores_pool_destroy": (None, [_P]),
+    "hg_stores_pool_bytes": (_SZ, [_P]),
+    "hg_stores_pool_append_device": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P, _P]),
+    "hg_stores_pool_select_capacity": (_SZ, [_P, ctypes.c_uint32]),
+    "hg_stores_pool_step_device": (_I, [_P, ctypes.c_uint32, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_stores_pool_count": (_I, [_P, ctypes.POINTER(_SZ)]),
+    "hg_stores_pool_read": (_I, [_P, ctypes.c_uint32, _SZ, _P, _P, _P, ctypes.POINTER(_SZ)]),
+    "hg_stores_pool_clear": (_I, [_P]),
     "hg_batcher_create": (_I, [_P, _SZ, ctypes.c_uint, ctypes.POINTER(_P)]),
     "hg_batcher_destroy": (None, [_P]),
     "hg_batcher_submit": (_I, [_P, _P, _SZ, _P, _P, _P, ctypes.POINTER(_P)]),

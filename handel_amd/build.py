@@ -23,7 +23,7 @@ SOURCES = ["bn256_verify.hip", "bn256_pair.hip", "bn256_kernels.hip", "bn256_gt.
            "bn256_sig16.hip", "bn256_sig12.hip", "bn256_sigw2.hip", "bn256_xprobe.hip", "bn256_xprobew2.hip", "bn256_fprobe.hip",
            "hg_api.cpp",
            "hg_aggregate.cpp", "hg_gttables.cpp", "hg_lanes.cpp", "hg_intake.cpp", "hg_batcher.cpp", "hg_packets.hip", "hg_service.cpp", "hg_stores.hip",
-           "hg_merge.hip", "bn256_msgs.hip", "bn256_aggmsgs.hip", "hg_msgs.cpp", "bn256_rlc.hip", "hg_rlc.cpp",
+           "hg_merge.hip", "hg_pool.hip", "hg_pool_api.cpp", "bn256_msgs.hip", "bn256_aggmsgs.hip", "hg_msgs.cpp", "bn256_rlc.hip", "hg_rlc.cpp",
            "bn256_msgsrlc.hip", "hg_msgs_rlc.cpp", "bn256_batchrlc.hip", "hg_batch_rlc.cpp"]
 # every header of csrc/: a change to any of them rebuilds the library
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))

@@ -4,7 +4,7 @@
 // (context, message, registry, single checks), hg_gttables.cpp (GT tables),
 // hg_aggregate.cpp (aggregate verification), hg_lanes.cpp (service lanes),
 // hg_rlc.cpp (its random-linear-combination form), hg_intake.cpp (packets,
-// stores), hg_msgs.cpp (checks on their own messages), hg_msgs_rlc.cpp (their
+// stores), hg_pool_api.cpp (the stores' standing queue), hg_msgs.cpp (checks on their own messages), hg_msgs_rlc.cpp (their
 // random-linear-combination form) and hg_batch_rlc.cpp (independent checks in
 // that form) include it. Every device resource below is held by an owner of
 // hg_dev.h, so deleting a context, a lane or a store set frees what it holds.

@@ -23,29 +23,13 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "hg_packets.h"
+#include "hg_store_mark.h"
 
 namespace hg {
 
 namespace {
 
-constexpr int kCntBits = 21;  // a count is at most 2^16 (kStoreMaxLevels): three per accumulator
-constexpr uint64_t kCntMask = (1ull << kCntBits) - 1;
 constexpr uint64_t kKeyNone = ~0ull;
-
-// the words of a `size`-bit set: word w keeps its bits below size
-__device__ inline uint64_t keep_below(uint64_t v, int w, uint32_t size) {
-  const uint32_t base = (uint32_t)w * 64u;
-  if (base >= size) return 0;
-  const uint32_t rem = size - base;
-  return rem < 64 ? v & ((1ull << rem) - 1) : v;
-}
-
-// (receiver, level) -> the level's range among the receiver's levels
-// (Partitioner.Levels = 1..ceil(log2 N), non-empty); false: no range
-__device__ inline bool store_range(const StoreTab& t, uint32_t receiver, uint32_t level, uint32_t& lo, uint32_t& hi) {
-  return receiver < t.nreg && level >= 1 && level <= (uint32_t)t.levels &&
-         pkt_range_level(receiver, t.nreg, (int)level, lo, hi);
-}
 
 }  // namespace
 
@@ -81,6 +65,11 @@ void launch_store_update(const StoreTab& t, const hg_store_update* ups, int n, c
 // ---------------------------------------------------------------- evaluate
 // tshift = log2(team). Every lane of a wave runs the same loop count and the
 // same shuffles; a slot that is not scored against a store loads nothing.
+// The counts and the mark below are hg_store_mark.h's mark_accumulate and
+// mark_from_counts written out: calling them here gives the same instructions
+// in another register allocation, and this kernel's machine code is held fixed
+// (tools/kernel_sizes.py --digest-masked). tests/test_gpu_pool.py holds the
+// two against each other.
 __global__ __launch_bounds__(256) void k_store_evaluate(StoreTab t, const hg_packet* pkts, int n, int slot_stride,
                                                         const uint64_t* words, const int32_t* codes,
                                                         const uint8_t* live, int32_t* scores, int tshift) {

@@ -974,6 +974,10 @@ class Stores:
 
     def close(self):
         if getattr(self, "h", None):
+            for ref in getattr(self, "_pools", []):  # pools go before their stores
+                pool = ref()
+                if pool is not None:
+                    pool.close()
             self.L.hg_stores_destroy(self.h)
             self.h = None
 
@@ -1096,6 +1100,84 @@ class Stores:
             self.engine._check(self.L.hg_stores_combined(self.h, _ptr(q), m, ws, _ptr(codes), _ptr(bitlens),
                                                          _ptr(words), _ptr(sigs)), "hg_stores_combined")
         return codes, bitlens, words, sigs
+
+
+class Pool:
+    """Handel's queue of parsed signatures kept in HBM across intake steps
+    (hg_stores_pool_*): `append_device` adds the admitted slots of a parsed
+    batch, `step_device` is one readTodos pass over the whole queue whose picks
+    come out as a parsed batch. The stores must outlive the pool (closing them
+    closes their pools first)."""
+
+    def __init__(self, stores: Stores, capacity_slots: int):
+        self.stores = stores
+        self.engine = stores.engine
+        self.L = stores.L
+        self.capacity_slots = int(capacity_slots)
+        h = ctypes.c_void_p()
+        rc = self.L.hg_stores_pool_create(stores.h, self.capacity_slots, ctypes.byref(h))
+        if rc != 0:
+            raise HandelGPUError(f"hg_stores_pool_create: code {rc}")
+        self.h = h
+        stores.__dict__.setdefault("_pools", []).append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hg_stores_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def bytes(self) -> int:
+        """Device memory the pool holds (hg_stores_pool_bytes)."""
+        return int(self.L.hg_stores_pool_bytes(self.h))
+
+    def append_device(self, d_pkts: int, n: int, stride: int, d_reqs: int, d_words: int, d_sigs: int, d_codes: int,
+                      d_live: int, stream: int = 0) -> None:
+        """hg_stores_pool_append_device on raw device pointers (asynchronous):
+        the outputs of one hg_parse_packets_device call."""
+        self.engine._check(self.L.hg_stores_pool_append_device(self.h, d_pkts or None, int(n), int(stride),
+                                                               d_reqs or None, d_words or None, d_sigs or None,
+                                                               d_codes or None, d_live or None, stream or None),
+                           "hg_stores_pool_append_device")
+
+    def select_capacity(self, k: int) -> int:
+        return int(self.L.hg_stores_pool_select_capacity(self.h, int(k)))
+
+    def step_device(self, k: int, capacity: int, d_out_pkts: int, d_sel: int, d_count: int, d_out_reqs: int,
+                    d_out_words: int, d_out_sigs: int, d_out_scores: int, stream: int = 0) -> None:
+        """hg_stores_pool_step_device on raw device pointers (asynchronous)."""
+        self.engine._check(self.L.hg_stores_pool_step_device(self.h, int(k), int(capacity), d_out_pkts or None,
+                                                             d_sel or None, d_count or None, d_out_reqs or None,
+                                                             d_out_words or None, d_out_sigs or None,
+                                                             d_out_scores or None, stream or None),
+                           "hg_stores_pool_step_device")
+
+    def count(self) -> int:
+        """Slots queued now (hg_stores_pool_count; synchronous)."""
+        n = ctypes.c_size_t()
+        self.engine._check(self.L.hg_stores_pool_count(self.h, ctypes.byref(n)), "hg_stores_pool_count")
+        return int(n.value)
+
+    def read(self, receiver: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(packet records, individual flags, last marks) of the receiver's
+        queued slots in queue order (hg_stores_pool_read)."""
+        cap = self.capacity_slots
+        pkts = np.zeros(cap, dtype=PACKET_DTYPE)
+        ind = np.zeros(cap, dtype=np.uint8)
+        scores = np.zeros(cap, dtype=np.int32)
+        n = ctypes.c_size_t()
+        self.engine._check(self.L.hg_stores_pool_read(self.h, int(receiver), cap, _ptr(pkts), _ptr(ind), _ptr(scores),
+                                                      ctypes.byref(n)), "hg_stores_pool_read")
+        m = int(n.value)
+        return pkts[:m], ind[:m], scores[:m]
+
+    def clear(self) -> None:
+        self.engine._check(self.L.hg_stores_pool_clear(self.h), "hg_stores_pool_clear")
 
 
 class DeviceLane:

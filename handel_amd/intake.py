@@ -27,7 +27,7 @@ import numpy as np
 from . import partitioner as part
 from ._lib import (HG_COMBINED_EMPTY, HG_MERGE_DISCARDED, HG_MERGE_STORED, HG_OK, HG_STORE_BEST_SIG,
                    HG_STORE_HAS_BEST, HG_STORE_LEVEL_FULL, HG_STORE_SIG_BEST, HandelGPUError)
-from .engine import REQ_DTYPE, STORE_SIG_DTYPE, STORE_UPDATE_DTYPE, Engine, Stores
+from .engine import PACKET_DTYPE, REQ_DTYPE, STORE_SIG_DTYPE, STORE_UPDATE_DTYPE, Engine, Pool, Stores
 from .packets import Packet, pack_packets
 from .sigprocessing import IncomingSig, IndividualSigFilter, MultiSig, Store, bits_to_int, int_to_words
 
@@ -78,6 +78,46 @@ def select_slots(store_of_slot: Sequence[int], scores: Sequence[int], n: int, k:
         picked += [slots[i] for i in p]
         rest += [slots[i] for i in r]
     return picked, rest
+
+
+class PoolModel:
+    """The standing queue on plain Python lists: one queue per receiver, one
+    `select_reference` per receiver and step. What hg_stores_pool_* is tested
+    against. An item is whatever the caller queues; `step` asks `evaluate` for
+    its mark."""
+
+    def __init__(self, receivers: Sequence[int]):
+        self.receivers = [int(r) for r in receivers]
+        self.queues: Dict[int, List[list]] = {r: [] for r in self.receivers}  # [item, mark of the last step]
+        self.disordered = 0  # (receiver, step) queues whose re-queued order was not their arrival order
+        self.dropped = 0     # slots that left with a mark <= 0
+
+    def append(self, receiver: int, item) -> bool:
+        """Queues an admitted item behind the receiver's queue; False: the receiver has no store."""
+        if receiver not in self.queues:
+            return False
+        self.queues[receiver].append([item, 0])
+        return True
+
+    def count(self) -> int:
+        return sum(len(q) for q in self.queues.values())
+
+    def queue(self, receiver: int) -> List[Tuple[object, int]]:
+        return [(it, mk) for it, mk in self.queues[receiver]]
+
+    def step(self, k: int, evaluate: Callable[[int, object], int]) -> List[Tuple[int, object, int]]:
+        """One readTodos pass per receiver, in receiver order: the picks as
+        (receiver, item, mark), best first inside a receiver."""
+        picks: List[Tuple[int, object, int]] = []
+        for r in self.receivers:
+            q = self.queues[r]
+            marks = [int(evaluate(r, it)) for it, _ in q]
+            p, rest = select_reference(marks, k)
+            picks += [(r, q[i][0], marks[i]) for i in p]
+            self.disordered += rest != sorted(rest)
+            self.dropped += sum(m <= 0 for m in marks)
+            self.queues[r] = [[q[i][0], marks[i]] for i in rest]
+        return picks
 
 
 class DeviceStores(Stores):
@@ -165,12 +205,26 @@ class DeviceIntake:
     `Store.store`, no `combine_g1`, no `mirror`. Only the merge results, the
     verdicts, scores, parse codes and the list of changed levels come back
     (`last_results`, `last_changed`); the host stores in `host` stay empty, and
-    `best` / `combined` / `full_signature` read the device."""
+    `best` / `combined` / `full_signature` read the device.
+
+    device_pool=True: the queue lives in HBM (hg_stores_pool_*, `pool_slots`
+    slots, default 4 * max_packets). A step packs, uploads and parses only the
+    new packets, appends their admitted slots to the pool, and one
+    hg_stores_pool_step_device scores the whole queue, hands out the picks as a
+    parsed batch (verified and, with device_merge, merged as it is) and
+    re-queues the rest on the device. Only the picks (records, bitsets,
+    signatures, verdicts) and the new packets' parse codes come back; no
+    `Packet` of an earlier step is kept and `select_slots` does not run. `step`
+    then returns the pool's count in place of `unselected`; `pending_view`
+    reads a receiver's queue back."""
 
     def __init__(self, engine: Engine, receivers: Sequence[int], k: int, max_packets: int = 4096,
-                 combine: Optional[Callable[[bytes, bytes], bytes]] = None, device_merge: bool = False):
+                 combine: Optional[Callable[[bytes, bytes], bytes]] = None, device_merge: bool = False,
+                 device_pool: bool = False, pool_slots: Optional[int] = None):
         if k < 1:
             raise ValueError("k must be >= 1")
+        if device_pool and k > 64:
+            raise ValueError("the device pool picks at most 64 slots per receiver")
         self.engine, self.k, self.max_packets = engine, int(k), int(max_packets)
         self.receivers = [int(r) for r in receivers]
         self.n = int(engine.L.hg_registry_size(engine.ctx))
@@ -187,9 +241,24 @@ class DeviceIntake:
         self.index = {r: i for i, r in enumerate(self.receivers)}
         # (packet, receiver, multisignature still queued, individual signature still queued)
         self.pending: List[Tuple[Packet, int, bool, bool]] = []
+        self.device_pool = bool(device_pool)
+        self.pool: Optional[Pool] = None
+        self.last_uploaded = 0  # packets the last pooled step packed and uploaded
+        if self.device_pool:
+            self.pool = Pool(self.stores, int(pool_slots) if pool_slots else 4 * self.max_packets)
 
     def close(self):
+        if self.pool is not None:
+            self.pool.close()
+            self.pool = None
         self.stores.close()
+
+    def pending_view(self, receiver: int) -> List[Tuple[int, int, bool, int]]:
+        """device_pool: the receiver's queue as (origin, level, individual, last mark), in queue order."""
+        if self.pool is None:
+            raise HandelGPUError("pending_view needs device_pool=True")
+        pkts, ind, marks = self.pool.read(receiver)
+        return [(int(p["origin"]), int(p["level"]), bool(i), int(m)) for p, i, m in zip(pkts, ind, marks)]
 
     def set_own(self, receiver: int, sig: bytes) -> None:
         """The receiver's own signature, its level 0 (handel.go:116)."""
@@ -243,6 +312,8 @@ class DeviceIntake:
 
         if len(packets) != len(receivers):
             raise ValueError("one receiver per packet")
+        if self.device_pool:
+            return self._step_pool(packets, receivers)
         batch = list(self.pending) + [(p, int(r), True, p.individual is not None) for p, r in zip(packets, receivers)]
         n, n_old = len(batch), len(self.pending)
         if n == 0:
@@ -327,3 +398,105 @@ class DeviceIntake:
         # the queue of the next step: one entry per waiting slot, in read_todos' order
         self.pending = [(batch[slot % n][0], batch[slot % n][1], slot < n, slot >= n) for slot in rest]
         return results, rest
+
+    def _step_pool(self, packets: Sequence[Packet], receivers: Sequence[int]):
+        """`step` with the queue in HBM: (results, slots left in the pool)."""
+        import torch
+
+        n = len(packets)
+        if n > self.max_packets:
+            raise ValueError(f"{n} packets exceed max_packets = {self.max_packets}")
+        eng, st, pool, stride = self.engine, self.stores, self.pool, self.stride
+        dev = torch.device("cuda", eng.device)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
+        recv = [int(r) for r in receivers]
+        fresh_ind = []  # new packets whose individual signature passed the filter now
+        d_pcodes = None
+        self.last_uploaded = n
+        if n:
+            live = np.ones(2 * n, dtype=np.uint8)
+            for i, (p, r) in enumerate(zip(packets, recv)):
+                want_ind = p.individual is not None
+                if want_ind and r in self.filters:
+                    want_ind = self.filters[r].accept(IncomingSig(p.origin, p.level, None, ind=True))
+                    if want_ind:
+                        fresh_ind.append(i)
+                live[n + i] = want_ind
+            wire, recs = pack_packets(list(packets), recv)
+            d_wire, d_pkts, d_live = up(np.frombuffer(wire, dtype=np.uint8)), up(recs), up(live)
+            d_reqs = torch.empty(2 * n * REQ_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            d_words = torch.empty(2 * n * stride, dtype=torch.int64, device=dev)
+            d_sigs = torch.empty(2 * n * 64, dtype=torch.uint8, device=dev)
+            d_pcodes = torch.empty(2 * n, dtype=torch.int32, device=dev)
+            eng.parse_packets_device(d_wire.data_ptr(), len(wire), d_pkts.data_ptr(), n, stride, d_reqs.data_ptr(),
+                                     d_words.data_ptr(), d_sigs.data_ptr(), d_pcodes.data_ptr(), s)
+            try:
+                pool.append_device(d_pkts.data_ptr(), n, stride, d_reqs.data_ptr(), d_words.data_ptr(),
+                                   d_sigs.data_ptr(), d_pcodes.data_ptr(), d_live.data_ptr(), s)
+            except HandelGPUError:
+                for i in fresh_ind:  # nothing was queued: the filter has not seen these
+                    self.filters[recv[i]].seen.pop(packets[i].origin, None)
+                raise
+        cap = pool.select_capacity(self.k)
+        d_opkts = torch.empty(cap * PACKET_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_sel = torch.empty(cap, dtype=torch.int32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_oreqs = torch.empty(cap * REQ_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_owords = torch.empty(2 * cap * stride, dtype=torch.int64, device=dev)
+        d_osigs = torch.empty(2 * cap * 64, dtype=torch.uint8, device=dev)
+        d_marks = torch.empty(cap, dtype=torch.int32, device=dev)
+        d_vcodes = torch.empty(cap, dtype=torch.int32, device=dev)
+        pool.step_device(self.k, cap, d_opkts.data_ptr(), d_sel.data_ptr(), d_count.data_ptr(), d_oreqs.data_ptr(),
+                         d_owords.data_ptr(), d_osigs.data_ptr(), d_marks.data_ptr(), s)
+        # the whole capacity without reading the count first: the filler fails the level check
+        eng.verify_aggregate_device(d_oreqs.data_ptr(), cap, d_owords.data_ptr(), d_osigs.data_ptr(),
+                                    d_vcodes.data_ptr(), stream=s)
+        if self.device_merge:
+            d_results = torch.empty(cap, dtype=torch.int32, device=dev)
+            d_changed = torch.empty(2 * cap, dtype=torch.int32, device=dev)
+            d_nchanged = torch.zeros(1, dtype=torch.int32, device=dev)
+            st.merge_device(d_opkts.data_ptr(), cap, d_sel.data_ptr(), d_count.data_ptr(), cap, d_vcodes.data_ptr(),
+                            stride, d_owords.data_ptr(), d_osigs.data_ptr(), d_results.data_ptr(),
+                            d_changed.data_ptr(), d_nchanged.data_ptr(), s)
+        torch.cuda.synchronize(dev)
+        count = int(d_count.cpu().numpy()[0])
+        sel = d_sel[:count].cpu().numpy().astype(np.int64)
+        vcodes = d_vcodes[:count].cpu().numpy()
+        opkts = np.frombuffer(d_opkts[:count * PACKET_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=PACKET_DTYPE)
+        oreqs = np.frombuffer(d_oreqs[:count * REQ_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=REQ_DTYPE)
+        owords = d_owords.view(2 * cap, stride).index_select(0, d_sel[:count].long()).cpu().numpy().view(np.uint64)
+        osigs = d_osigs[:count * 64].cpu().numpy().reshape(count, 64)
+        if d_pcodes is not None:
+            pcodes = d_pcodes.cpu().numpy()
+            for i in fresh_ind:  # a packet that failed to parse never reached the filter
+                if pcodes[i] != HG_OK:
+                    self.filters[recv[i]].seen.pop(packets[i].origin, None)
+        results, changed = [], {}
+        if self.device_merge:
+            merged = d_results.cpu().numpy()[:count]
+            nch = int(d_nchanged.cpu().numpy()[0])
+            self.last_results = merged.tolist()
+            self.last_changed = [tuple(x) for x in d_changed.cpu().numpy()[:2 * nch].reshape(-1, 2).tolist()]
+        for e in range(count):
+            r, origin, level = int(opkts[e]["receiver"]), int(opkts[e]["origin"]), int(opkts[e]["level"])
+            sig = osigs[e].tobytes()
+            if sel[e] >= cap:
+                lo, hi = part.range_level(r, self.n, level)
+                sp = IncomingSig(origin, level, MultiSig(hi - lo, 1 << (origin - lo), sig), ind=True,
+                                 mapped_index=origin - lo)
+            else:
+                bits = int.from_bytes(owords[e].astype("<u8").tobytes(), "little")
+                sp = IncomingSig(origin, level, MultiSig(int(oreqs[e]["bitlen"]), bits, sig))
+            code = int(vcodes[e])
+            err = None if code == HG_OK else eng.processing_error_string(code)
+            if self.device_merge:
+                if err is None and merged[e] not in (HG_MERGE_STORED, HG_MERGE_DISCARDED):
+                    err = f"device merge: result {int(merged[e])}"
+            elif err is None:
+                self.host[r].store(sp)
+                changed.setdefault(r, set()).add(sp.level)
+            results.append((r, sp, err))
+        if changed:
+            st.mirror_many([(r, self.host[r], lv) for r, lv in changed.items()])
+        return results, pool.count()

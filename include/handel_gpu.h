@@ -861,6 +861,88 @@ int hg_stores_combined_device(hg_stores* st, const hg_store_query* d_queries, si
 int hg_stores_combined(hg_stores* st, const hg_store_query* queries, size_t m, size_t words_stride, int32_t* codes,
                        uint32_t* bitlens, uint64_t* words, uint8_t* sigs);
 
+/* ---------------------------------------------------------------- stores: the standing queue
+ * Opt-in: Handel's queue of parsed signatures in HBM. readTodos
+ * (processing.go:171-220) verifies the best signatures of a pass and keeps
+ * every other one of positive mark for the next. A pool holds those slots on
+ * the device between intake steps: hg_stores_pool_append_device adds the
+ * admitted slots of a parsed batch, hg_stores_pool_step_device scores every
+ * pooled slot against the stores as they are now, hands out the k best per
+ * store as a parsed batch (for hg_verify_aggregate_device and
+ * hg_stores_merge_device) and re-queues the rest in readTodos' order. A pooled
+ * slot holds its packet's origin, receiver, level and flags, whether it is the
+ * individual slot, its request's offset, bitlen and level_size (32 bytes),
+ * hg_packet_stride_words bitset words, the 64-byte signature and its last
+ * mark; its place in its receiver's queue is its index (among one receiver's
+ * slots a lower index is earlier). The pool keeps two such sides, a step
+ * writing the survivors from one to the other.
+ * A pool belongs to one hg_stores and through it to one context and registry:
+ * after a later hg_registry_load every call returns HG_ERR_ARG. Every call is
+ * a submission of the context. Destroy the pool before its stores. */
+typedef struct hg_pool hg_pool;
+/* capacity_slots >= 1 (at most 2^25). Everything the pool needs, workspaces
+ * included, is allocated here; no later call allocates device memory. */
+int hg_stores_pool_create(hg_stores* st, size_t capacity_slots, hg_pool** out);
+void hg_stores_pool_destroy(hg_pool* pool);
+/* Device memory the pool holds, in bytes. */
+size_t hg_stores_pool_bytes(hg_pool* pool);
+/* Appends the slots of one hg_parse_packets_device call (its inputs d_pkts, n,
+ * stride_words and its outputs). A slot is admitted if and only if its code is
+ * HG_OK, its d_live byte (nullable, 2n bytes) is not 0, its (receiver, level)
+ * has a range and its receiver has a store: the slots hg_stores_evaluate_device
+ * scores against a store. Admitted slots are queued in Handel's queue order,
+ * 2*(slot mod n) + (slot >= n), each behind everything its receiver already
+ * has queued. Asynchronous on `stream`. The pool keeps a host-side bound on
+ * its occupancy: the last count it read back plus every slot offered since.
+ * When the bound plus 2n exceeds the capacity the call reads the true count
+ * (one synchronisation of the stream); when 2n still does not fit it returns
+ * HG_ERR_ARG and appends nothing. Whatever the host believes, no kernel writes
+ * at an index at or above the capacity. d_sigs 4-byte aligned. */
+int hg_stores_pool_append_device(hg_pool* pool, const hg_packet* d_pkts, size_t n, size_t stride_words,
+                                 const hg_request* d_reqs, const uint64_t* d_words, const uint8_t* d_sigs,
+                                 const int32_t* d_codes, const uint8_t* d_live, void* stream);
+/* Entries hg_stores_pool_step_device writes: min(capacity_slots, n_receivers * k). */
+size_t hg_stores_pool_select_capacity(hg_pool* pool, uint32_t k);
+/* One pass of readTodos with k slots per store (1 <= k <= 64) over the whole
+ * pool. Every pooled slot gets store.go:111-183 unsafeEvaluate's mark against
+ * the stores as they are now. Per store at most k slots of mark > 0 are
+ * picked, highest mark first, equal marks by earlier queue place; the output
+ * is grouped by store in creation order (hg_stores_select_device's rule and
+ * order). The picks and every slot of mark <= 0 leave the pool; the others
+ * stay, per store in the order readTodos re-queues them (a slot that loses on
+ * arrival is appended when it is met, one pushed out of the k held when it is
+ * pushed out). The output is a parsed batch of `capacity` packets, capacity =
+ * hg_stores_pool_select_capacity(pool, k) <= the store set's max_packets
+ * (else HG_ERR_ARG): entry e < *d_count has its packet record (pool offsets
+ * zero) in d_out_pkts[e]; its slot d_sel[e] is e for a multisignature and
+ * capacity + e for an individual signature; d_out_reqs[e].word_offset =
+ * d_sel[e] * hg_packet_stride_words, its words at that slot of d_out_words
+ * (2 * capacity slots), its signature at 64 * e and, for an individual slot,
+ * also at 64 * (capacity + e) of d_out_sigs (2 * capacity * 64 bytes, 4-byte
+ * aligned); d_out_scores[e] is its mark. Entries from *d_count on are
+ * hg_stores_select_device's filler: slot 0xffffffff, request {0, 0, 1, 0}, a
+ * zero signature, a zero record and mark. So
+ * hg_verify_aggregate_device(d_out_reqs, capacity, d_out_words, d_out_sigs, ..)
+ * and hg_stores_merge_device(st, d_out_pkts, capacity, d_sel, d_count,
+ * capacity, d_vcodes, stride, d_out_words, d_out_sigs, ..) run on the output
+ * as it is. Slots of d_out_words and d_out_sigs that no entry names are not
+ * written. Asynchronous on `stream`; the same pool state and stores give the
+ * same output. */
+int hg_stores_pool_step_device(hg_pool* pool, uint32_t k, size_t capacity, hg_packet* d_out_pkts, uint32_t* d_sel,
+                               uint32_t* d_count, hg_request* d_out_reqs, uint64_t* d_out_words, uint8_t* d_out_sigs,
+                               int32_t* d_out_scores, void* stream);
+/* Slots queued now. Synchronous; refreshes the host-side bound. */
+int hg_stores_pool_count(hg_pool* pool, size_t* count);
+/* Read-back for tests and diagnosis: the queued slots of one hosted receiver
+ * in queue order, the first `cap` of them: packet record, whether it is the
+ * individual slot, and the mark it got in the last step (0 for a slot
+ * appended since); each array nullable. *count: how many the receiver has
+ * queued. Synchronous. */
+int hg_stores_pool_read(hg_pool* pool, uint32_t receiver, size_t cap, hg_packet* pkts, uint8_t* individual,
+                        int32_t* scores, size_t* count);
+/* Empties the pool. Synchronous. */
+int hg_stores_pool_clear(hg_pool* pool);
+
 /* ---------------------------------------------------------------- batcher
  * A launch-merging request queue on one context, for callers that verify one
  * multisignature at a time: each Handel instance's processLoop checks one
